@@ -8,7 +8,18 @@ partials -> rank 0 multiplies them and runs one final exponentiation.  This is
 config 5's per-GPU shard (1,048,576 sets over 8 GPUs = 131,072 per GPU) with
 weak scaling; inputs are resident in HBM before the timed region.
 
-Also reported on rank 0 (extra keys of the same JSON line):
+A plain run does only that: it sets up, warms up, times the steps, writes its
+outputs when --dump-outputs DIR is given, and prints the result line.
+
+--dump-outputs DIR writes what the last timed step computed, as float32 .npy
+files: `partial_fp12` (rank 0's partial Miller product, the 12 Fp coordinates
+of the record decoded to canonical form, 48 big-endian byte values each; the
+product is defined up to the factors the final exponentiation removes),
+`partial_invalid_sets` (the record's count of invalid sets) and `verdict`
+(1.0: the batch verified).  The workload and its randomizers are seeded, so
+two runs with the same arguments hold the same inputs.
+
+With --full, also reported on rank 0 (extra keys of the same JSON line):
   * config 1: p50/p99 latency of a 128-set batchVerify through the host C ABI
     (API entry -> boolean, PCIe upload included), >= 100 repetitions;
   * config 2: 64 x 512-key fastAggregateVerify (tbls_fast_aggregate_verify_many);
@@ -19,15 +30,18 @@ Also reported on rank 0 (extra keys of the same JSON line):
   * the per-stage kernel times and the integer-MAC roofline of the dominant
     kernel on SURVEY.md 8(d)'s model (300 MAC per Fp product);
   * the CPU baseline: the C oracle timed on this host's cores (N threads and
-    1 thread, CPU model stated) on a bounded sample of the same workload.
+    1 thread, CPU model stated) on a bounded sample of the same workload;
+  * the same steps with the keys from the device-resident key table, config 5
+    at 1,048,576 sets as one batch, and the EIP-4844 KZG leg.
 
-python bench.py --gpus N --steps K --warmup W
+python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 """
 
 import argparse
 import ctypes
 import json
 import os
+import random
 import statistics
 import sys
 import time
@@ -585,12 +599,39 @@ def kzg_leg(device, reps, cpu_sample):
     return out
 
 
+def dump_outputs(path, records, world, verdict):
+    """What a caller of the timed path receives from its last step, as float32
+    .npy files under `path`: the partial records of all ranks (gathered on
+    rank 0) and the verdict of the final exponentiation.  The records' Fp
+    coordinates are decoded from the kernels' weakly reduced Montgomery limbs
+    to canonical integers, so two builds that compute the same product write
+    the same file whatever representative their last reduction left."""
+    import numpy as np
+
+    from teku_amd.dist import decode_partial
+
+    os.makedirs(path, exist_ok=True)
+    fp12 = np.zeros((world, 12, 48), dtype=np.float32)
+    bad = np.zeros(world, dtype=np.float32)
+    for r in range(world):
+        f, n_bad = decode_partial(records[native.PARTIAL_BYTES * r : native.PARTIAL_BYTES * (r + 1)])
+        coords = [v for fp6 in f for fp2 in fp6 for v in fp2]
+        fp12[r] = np.frombuffer(b"".join(v.to_bytes(48, "big") for v in coords), dtype=np.uint8).reshape(12, 48)
+        bad[r] = n_bad
+    np.save(os.path.join(path, "partial_fp12.npy"), fp12)
+    np.save(os.path.join(path, "partial_invalid_sets.npy"), bad)
+    np.save(os.path.join(path, "verdict.npy"), np.array([float(verdict)], dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--sets-per-gpu", type=int, default=int(os.environ.get("TBLS_SETS_PER_GPU", 131072)))
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true", help="also run every other leg: stage times and roofline, key table, 1M-set batch, "
+                    "configs 1-4, KZG, CPU baselines (the --no-* options below trim it)")
     ap.add_argument("--lat-reps", type=int, default=100)
     ap.add_argument("--extra-reps", type=int, default=20)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -617,7 +658,9 @@ def main():
     t_gen = time.perf_counter()
     lo, hi = shard_bounds(S * world, world, rank)  # weak scaling: S sets per rank
     pks, msgs, sigs = synth.single_signer(lo, hi - lo)
-    batch = DevBatch(pks, [1] * S, msgs, [32] * S, sigs, device)
+    # seeded randomizers (the same inputs from run to run, so two builds compare output for output)
+    rands = synth.random_multipliers(S, random.Random(0x7EC0 + rank))
+    batch = DevBatch(pks, [1] * S, msgs, [32] * S, sigs, device, rands)
     gen_s = time.perf_counter() - t_gen
     partial = torch.empty(native.PARTIAL_BYTES, dtype=torch.uint8, device=device)
     stream = torch.cuda.current_stream(device).cuda_stream
@@ -640,21 +683,25 @@ def main():
             native.check(L.tbls_dev_final_verify(local, src.data_ptr(), world, stream, ctypes.byref(ok)), "final")
             if ok.value != 1:
                 raise RuntimeError("valid synthetic batch rejected")
+        return src
 
     for _ in range(args.warmup):
         step(False)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
+    src = partial
     t0 = time.perf_counter()
     for _ in range(args.steps):  # the plain partial: no stage events inside the timed region
-        step(args.serial)
+        src = step(args.serial)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, bytes(src.cpu().numpy()), world, ok.value)
     stage_steps = 2 if not args.serial else args.steps  # the overlapped stage times from two event-timed steps after it
-    if not args.serial:
+    if args.full and not args.serial:
         for _ in range(stage_steps):
             step(True)
     if world > 1:
@@ -664,6 +711,35 @@ def main():
 
     total_sets = S * world * args.steps
     value = total_sets / dt
+    ms_per_step = dt / args.steps * 1e3
+    line = {
+        "metric": "BLS sigs verified/sec (batchVerify), 1-8 GPUs; p50 latency @128-sig batch",
+        "value": value,
+        "unit": "sigs/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u32 (381-bit Montgomery Fp, 14x29-bit limb products)",
+        "data": "synthetic: interop keys (first 65,536 reused cyclically), distinct sha256 messages, GPU-signed",
+        "config": {
+            "workload": "config 5 per-GPU shard: randomized batchVerify of %d single-signer sets per GPU, RCCL Fp12 partial gather, 1 final exp" % S,
+            "sets_per_gpu": S,
+            "parallelism": "data-parallel shards, dp%d" % world,
+        },
+        "serial_stages": bool(args.serial),
+        "workload_gen_s": gen_s,
+    }
+    if not args.full:  # the plain run: the headline figure only
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # Same steps with the keys in the device-resident validator table
     # (tbls_pk_table_load / tbls_dev_batch_partial_idx):
@@ -731,7 +807,7 @@ def main():
         one_m = {"value": n1m / dt1m, "unit": "sigs/s", "ms_per_batch": dt1m * 1e3, "steps": k1m, "gen_s": gen1,
                  "what": "config 5 at 1,048,576 sets as ONE device batch on this GPU (partial + final exponentiation, inputs in HBM)"}
         del b1m
-        batch = DevBatch(pks, [1] * S, msgs, [32] * S, sigs, device)  # the profiled steps below use the 131k shard
+        batch = DevBatch(pks, [1] * S, msgs, [32] * S, sigs, device, rands)  # the profiled steps below use the 131k shard
 
     stage_ms = [a / stage_steps for a in stage_acc]
     # Exclusive per-stage kernel times (every stage alone on the stream): the
@@ -742,7 +818,6 @@ def main():
         native.check(L.tbls_dev_batch_stage_profile(local, ctypes.byref(batch.desc), stream, partial.data_ptr(), stage), "profile")
         for i in range(len(STAGES)):
             excl[i] += stage[i] / 2
-    ms_per_step = dt / args.steps * 1e3
     roofline = roofline_entry(excl, S, device, ms_per_step)
 
     # config 1: latency of a 128-set batchVerify through the host C ABI
@@ -759,25 +834,7 @@ def main():
                               % os.environ.get("GPU_MAX_HW_QUEUES"))
 
     cpu = None if args.no_cpu_baseline else cpu_baseline_oracle(pks, msgs, sigs, min(4096, S), min(512, S))
-    line = {
-        "metric": "BLS sigs verified/sec (batchVerify), 1-8 GPUs; p50 latency @128-sig batch",
-        "value": value,
-        "unit": "sigs/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u32 (381-bit Montgomery Fp, 14x29-bit limb products)",
-        "data": "synthetic: interop keys (first 65,536 reused cyclically), distinct sha256 messages, GPU-signed",
-        "config": {
-            "workload": "config 5 per-GPU shard: randomized batchVerify of %d single-signer sets per GPU, RCCL Fp12 partial gather, 1 final exp" % S,
-            "sets_per_gpu": S,
-            "parallelism": "data-parallel shards, dp%d" % world,
-        },
-        "serial_stages": bool(args.serial),
+    line.update({
         "value_1m": one_m["value"] if one_m else None,
         "config5_1m": one_m,
         "value_key_table": total_sets / dt_tab,
@@ -793,8 +850,7 @@ def main():
         "configs": extra,
         "kzg": kzg_out,
         "cpu_baseline": cpu,
-        "workload_gen_s": gen_s,
-    }
+    })
     print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 O=$GRAFT_REPO_ROOT/gpurun_out
 TAG=${TAG:-ab}
 mkdir -p $O
-ARGS="--steps 3 --warmup 1 --no-extra --no-kzg --no-cpu-baseline --lat-reps 0"
+ARGS="--full --steps 3 --warmup 1 --no-extra --no-kzg --no-cpu-baseline --lat-reps 0"
 echo "== variant $VAR" && TBLS_LIB=$VAR timeout -k 10 300 python bench.py $ARGS > $O/ab_var_$TAG.json 2> $O/ab_var_$TAG.err; rc=$?; python -c "import json; d=json.load(open('$O/ab_var_$TAG.json')); print(round(d['ms_per_step'],3), {k:round(v,3) for k,v in d['stage_ms_exclusive'].items()})"; [ $rc -eq 0 ] || exit $rc
 echo "== main" && timeout -k 10 300 python bench.py $ARGS > $O/ab_main_$TAG.json 2> $O/ab_main_$TAG.err; rc=$?; python -c "import json; d=json.load(open('$O/ab_main_$TAG.json')); print(round(d['ms_per_step'],3), {k:round(v,3) for k,v in d['stage_ms_exclusive'].items()})"; [ $rc -eq 0 ] || exit $rc
 TAG=$TAG bash tools/gpu_time.sh || exit $?

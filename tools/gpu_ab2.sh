@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 O=$GRAFT_REPO_ROOT/gpurun_out
 TAG=${TAG:-ab2}
 mkdir -p $O
-ARGS="--steps 10 --warmup 3 --no-extra --no-kzg --no-1m --no-cpu-baseline --lat-reps ${LAT:-0}"
+ARGS="--full --steps 10 --warmup 3 --no-extra --no-kzg --no-1m --no-cpu-baseline --lat-reps ${LAT:-0}"
 show() { python -c "import json; d=json.load(open('$1')); print('$2', round(d['ms_per_step'],3), 'p50', d.get('p50_latency_ms_128'), {k:round(v,3) for k,v in d['stage_ms_exclusive'].items()})"; }
 for r in 1 2; do
   timeout -k 10 300 python bench.py $ARGS > $O/ab2_main_${TAG}_$r.json 2> $O/ab2_main_${TAG}_$r.err || exit $?

@@ -1,5 +1,5 @@
 #!/bin/bash
-# One GPU session: parity tests, the default bench line, rocprofv3 kernel-trace
+# One GPU session: parity tests, the full bench line (--full), rocprofv3 kernel-trace
 # stats of the same bench command, then PMC passes (each its own run, as
 # MI355X_MICROARCH.md prescribes): FETCH_SIZE, WRITE_SIZE, SQ counters.
 set -o pipefail
@@ -7,6 +7,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 SETS=${SETS:-131072}
+SETS="$SETS --full"  # every bench call below takes "--sets-per-gpu $SETS": all of them run every leg (--full)
 PARGS="--steps 1 --warmup 0 --sets-per-gpu $SETS --lat-reps 0 --no-cpu-baseline --no-1m --no-extra --no-kzg"
 echo "== pytest -m gpu" && timeout -k 10 900 python -u -m pytest tests -x -v -m gpu --timeout 120 --timeout-method thread > gpurun_out/pytest_gpu.log 2>&1; rc=$?; tail -4 gpurun_out/pytest_gpu.log; [ $rc -eq 0 ] || exit $rc
 echo "== bench" && timeout -k 10 600 python bench.py --sets-per-gpu $SETS > gpurun_out/bench.json 2> gpurun_out/bench.err; rc=$?; cat gpurun_out/bench.json; tail -3 gpurun_out/bench.err; [ $rc -eq 0 ] || exit $rc

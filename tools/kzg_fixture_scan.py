@@ -53,10 +53,29 @@ def triples(obj):
     return out
 
 
-def main(ref):
+def load_setup():
     from oracle import kzg_oracle as K
 
-    setup = K.Setup.from_file(os.path.join(ROOT, "tests", "golden", "kzg", "trusted_setup.txt"))
+    return K.Setup.from_file(os.path.join(ROOT, "tests", "golden", "kzg", "trusted_setup.txt"))
+
+
+def triple_report(setup, i, blob, com, proof):
+    """One triple's entry of the report (tests/test_kzg_fixture_scan.py runs it
+    over the blobs stored under tests/golden/kzg/fixture_blobs/)."""
+    canon = len(blob) == BLOB and all(int.from_bytes(blob[32 * k:32 * k + 32], "big") < R for k in range(BLOB // 32))
+    res = setup.verify_blob_kzg_proof(blob, com, proof) if len(blob) == BLOB and len(com) == 48 and len(proof) == 48 else "bad sizes"
+    return {
+        "index": i,
+        "blob_sha256": hashlib.sha256(blob).hexdigest(),
+        "blob_canonical": canon,
+        "commitment": com.hex(),
+        "proof": proof.hex(),
+        "verify_blob_kzg_proof": res if isinstance(res, (bool, str)) else f"error code {res}",
+    }
+
+
+def main(ref):
+    setup = load_setup()
     report = {"reference": ref, "files": []}
     for d, _, files in os.walk(ref):
         for f in sorted(files):
@@ -77,17 +96,7 @@ def main(ref):
             entry = {"file": os.path.relpath(p, ref), "triples": []}
             for blobs, coms, proofs in found:
                 for i, (b, c, pr) in enumerate(zip(blobs, coms, proofs)):
-                    blob, com, proof = hexb(b), hexb(c), hexb(pr)
-                    canon = len(blob) == BLOB and all(int.from_bytes(blob[32 * k:32 * k + 32], "big") < R for k in range(BLOB // 32))
-                    res = setup.verify_blob_kzg_proof(blob, com, proof) if len(blob) == BLOB and len(com) == 48 and len(proof) == 48 else "bad sizes"
-                    entry["triples"].append({
-                        "index": i,
-                        "blob_sha256": hashlib.sha256(blob).hexdigest(),
-                        "blob_canonical": canon,
-                        "commitment": com.hex(),
-                        "proof": proof.hex(),
-                        "verify_blob_kzg_proof": res if isinstance(res, (bool, str)) else f"error code {res}",
-                    })
+                    entry["triples"].append(triple_report(setup, i, hexb(b), hexb(c), hexb(pr)))
             report["files"].append(entry)
     n = sum(len(e["triples"]) for e in report["files"])
     ok = sum(1 for e in report["files"] for t in e["triples"] if t["verify_blob_kzg_proof"] is True)
