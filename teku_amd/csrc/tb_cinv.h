@@ -158,10 +158,20 @@ TBC_FN c32 shift30(const c64& c) {
   return coop::narrow(split_lo(x) + coop::wide(coop::shr<1>(coop::narrow(split_hi(x)))));
 }
 
-// Every lane of the row: a^-1 for a (any fp < 2p, the same on every lane);
-// the row's lanes write their limbs of d and f to buf (16 int32), lane 0
-// normalizes them and returns the result (the other lanes' return values are
-// unspecified).
+// Every lane of the row: a^-1 for a (the same on every lane); the row's lanes
+// write their limbs of d and f to buf (16 int32), lane 0 normalizes them and
+// returns the result (the other lanes' return values are unspecified).
+//
+// Contract: the raw limbs of a are in [0, 2p) and are NOT the raw value p.
+// a = 0 returns 0 (all limbs zero); the raw value p is a zero residue the
+// divsteps do not see as zero (g = f: they end with f = p, not +-1) and
+// returns a non-zero residue where fp_inv returns 0.  Every caller obtains a
+// from coop::cdigits_to_fp, which returns exactly 0 -- never p -- for every
+// zero residue in its range (all k p, |k| <= 64).  Two tests pin the two
+// halves, on the host emulation (tests/test_coop.py) and on the GPU
+// (tests/test_gpu_coop.py): the zero-residue test of cdigits_to_fp, and the
+// raw-limb inversion test over [0, 2p) without p, which also demands the same
+// limbs from both forms (U or not) at every row position of a wave.
 template <bool U = false>
 TBC_FN fp inv_row_lane0(const fp& a, int32_t* buf) {
   // g = a in 30-bit limbs: limb j = bits [30 j, 30 j + 30) of the 12 words
@@ -250,7 +260,10 @@ TBC_FN fp inv_row_lane0(const fp& a, int32_t* buf) {
   TB_UNROLL for (int j = 0; j < 12; j++) lo.l[j] = w[j];
   hi.l[0] = w[12];  // d + 64 p < 2^388: the bits above 384
   const fp t = fp_add(fp_mul(lo, fp_from_const(R3_MOD)), fp_mul(hi, fp_from_const(R3_2_384)));
-  return cfv < 0 ? fp_neg(t) : t;
+  const fp z = cfv < 0 ? fp_neg(t) : t;
+  // a = 0: d = 0 comes out of the products as the raw value p; return 0 itself
+  // (no other input in the contract has a zero inverse)
+  return fp_sel(fp_is_zero(z), fp_zero(), z);
 }
 
 }  // namespace cinv

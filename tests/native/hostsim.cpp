@@ -114,12 +114,24 @@ extern "C" int tbls_hostsim_coop_reduce(const int64_t* x, int32_t* out, size_t n
   return 0;
 }
 
-// ---- lane-cooperative point arithmetic (tb_cpoint.h) -----------------------
-#include "../../teku_amd/csrc/tb_cpoint.h"
+// the row inversion (tb_cinv.h) on raw limbs: a = n x 12 words in [0, 2p), not
+// the raw value p (no Montgomery conversion); u != 0: the form with the early
+// exit (inv_row_lane0<true>).  out = n x 12 raw words
+extern "C" int tbls_hostsim_coop_inv_raw(int u, const uint32_t* a, uint32_t* out, size_t n) {
+  for (size_t k = 0; k < n; k++) {
+    tb::fp x;
+    for (int j = 0; j < 12; j++) x.l[j] = a[12 * k + j];
+    const tb::fp z = u ? tb::cinv::inv_row_lane0<true>(x, nullptr) : tb::cinv::inv_row_lane0<false>(x, nullptr);
+    for (int j = 0; j < 12; j++) out[12 * k + j] = z.l[j];
+  }
+  return 0;
+}
 
-// G1: in = n x (x1, y1, x2, y2) Montgomery words (12 each); out = n x (X, Y, Z)
-// op 0: dbl(P1)  1: madd(dbl(P1), P2)  2: add(dbl(P1), dbl(P2))  3: [k] P1
-// (mul_u64_aff)  4: [k] dbl(P1) (mul_u64)  5: [k]([k] P1)
+// ---- lane-cooperative point arithmetic (tb_cpoint.h) -----------------------
+#include "tb_cpoint_ops.h"
+
+// G1: in = n x (x1, y1, x2, y2) Montgomery words (12 each); out = n x (X, Y, Z);
+// the ops of tb_cpoint_ops.h
 extern "C" int tbls_hostsim_cpoint_g1(int op, const uint32_t* in, uint32_t* out, size_t n, uint64_t k) {
   using namespace tb::coop;
   const cctx K = cctx_load();
@@ -127,16 +139,7 @@ extern "C" int tbls_hostsim_cpoint_g1(int op, const uint32_t* in, uint32_t* out,
   for (size_t i = 0; i < n; i++) {
     const uint32_t* w = in + 48 * i;
     const c32 x1 = cfrom_words(w), y1 = cfrom_words(w + 12), x2 = cfrom_words(w + 24), y2 = cfrom_words(w + 36);
-    const cj1 p1 = {x1, y1, one}, p2 = {x2, y2, one};
-    cj1 r;
-    switch (op) {
-      case 0: r = dbl(p1, K); break;
-      case 1: r = madd(dbl(p1, K), x2, y2, K); break;
-      case 2: r = add(dbl(p1, K), dbl(p2, K), K); break;
-      case 3: r = mul_u64_aff(x1, y1, k, one, K); break;
-      case 4: r = mul_u64(dbl(p1, K), k, K); break;
-      default: r = mul_u64(mul_u64_aff(x1, y1, k, one, K), k, K); break;
-    }
+    const cj1 r = cpoint_op<cj1, c32>(op, x1, y1, x2, y2, one, k, K);
     const c32* c[3] = {&r.x, &r.y, &r.z};
     for (int j = 0; j < 3; j++) {
       const tb::fp f = cdigits_to_fp(c[j]->v);
@@ -147,7 +150,6 @@ extern "C" int tbls_hostsim_cpoint_g1(int op, const uint32_t* in, uint32_t* out,
 }
 
 // G2: in = n x (x1, y1, x2, y2) as Fp2 (c0, c1) Montgomery words; out = n x (X, Y, Z)
-// op 0: dbl(P1)  1: madd(dbl(P1), P2)  3: [k] P1 (mul_u64_aff)
 extern "C" int tbls_hostsim_cpoint_g2(int op, const uint32_t* in, uint32_t* out, size_t n, uint64_t k) {
   using namespace tb::coop;
   const cctx K = cctx_load();
@@ -156,13 +158,7 @@ extern "C" int tbls_hostsim_cpoint_g2(int op, const uint32_t* in, uint32_t* out,
     const uint32_t* w = in + 96 * i;
     c2 v[4];
     for (int j = 0; j < 4; j++) v[j] = {cfrom_words(w + 24 * j), cfrom_words(w + 24 * j + 12)};
-    const cj2 p1 = {v[0], v[1], one};
-    cj2 r;
-    switch (op) {
-      case 0: r = dbl(p1, K); break;
-      case 1: r = madd(dbl(p1, K), v[2], v[3], K); break;
-      default: r = mul_u64_aff(v[0], v[1], k, one, K); break;
-    }
+    const cj2 r = cpoint_op<cj2, c2>(op, v[0], v[1], v[2], v[3], one, k, K);
     const c32* c[6] = {&r.x.c0, &r.x.c1, &r.y.c0, &r.y.c1, &r.z.c0, &r.z.c1};
     for (int j = 0; j < 6; j++) {
       const tb::fp f = cdigits_to_fp(c[j]->v);

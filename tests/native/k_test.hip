@@ -115,12 +115,28 @@ extern "C" __global__ void k_test_coop_timing(const uint8_t* in, uint8_t* out);
 extern "C" __global__ void k_test_coop_inv(const uint8_t* in, uint8_t* out, uint32_t n);
 extern "C" __global__ void k_test_final_exp_coop(const uint8_t* in, uint8_t* out);
 extern "C" __global__ void k_test_cfe_ops(const uint8_t* in, uint8_t* out);
+extern "C" __global__ void k_test_coop_mul_digits(const uint8_t* in, uint8_t* out, uint32_t n);
+extern "C" __global__ void k_test_coop_mul_words(const uint8_t* in, uint8_t* out, uint32_t n);
+extern "C" __global__ void k_test_coop_to_fp(const uint8_t* in, uint8_t* out, uint32_t n);
+extern "C" __global__ void k_test_coop_reduce(const uint8_t* in, uint8_t* out, uint32_t n);
+extern "C" __global__ void k_test_coop_inv_raw(const uint8_t* in, uint8_t* out, uint32_t n);
+extern "C" __global__ void k_test_coop_inv_u(const uint8_t* in, uint8_t* out);
+extern "C" __global__ void k_test_cpoint_g1(const uint8_t* in, uint8_t* out, uint32_t n);
+extern "C" __global__ void k_test_cpoint_g2(const uint8_t* in, uint8_t* out, uint32_t n);
 
 #define TOP_FINAL_EXP_COOP 45
 #define TOP_CFE_OPS 46
 #define TOP_COOP_MUL 43
 #define TOP_COOP_TIMING 44
 #define TOP_COOP_INV 47
+#define TOP_COOP_MUL_DIGITS 48
+#define TOP_COOP_MUL_WORDS 49
+#define TOP_COOP_TO_FP 50
+#define TOP_COOP_REDUCE 51
+#define TOP_COOP_INV_RAW 52
+#define TOP_COOP_INV_U 53
+#define TOP_COOP_POINT_G1 54
+#define TOP_COOP_POINT_G2 55
 #define TOP_FINAL_EXP_WAVE 29
 #define TOP_MILLER_WAVE 31
 #define TOP_MILLER_PROG 40  // tb_testops.h uses 1..35
@@ -135,6 +151,7 @@ extern "C" int tbls_test_ops(int op, const uint8_t* in, uint8_t* out, size_t n) 
   int rc = 8;
   if (hipMalloc(&din, n * TB_TEST_IN) == hipSuccess && hipMalloc(&dout, n * TB_TEST_OUT) == hipSuccess &&
       hipMemcpy(din, in, n * TB_TEST_IN, hipMemcpyHostToDevice) == hipSuccess && hipMemset(dout, 0, n * TB_TEST_OUT) == hipSuccess) {
+    const dim3 rows4((uint32_t)((n + 3) / 4));  // one record per 16-lane row
     if (op == TOP_FINAL_EXP_WAVE)
       hipLaunchKernelGGL(k_test_final_exp_wave, dim3((uint32_t)n), dim3(64), 0, 0, din, dout);
     else if (op == TOP_MILLER_WAVE)
@@ -153,6 +170,22 @@ extern "C" int tbls_test_ops(int op, const uint8_t* in, uint8_t* out, size_t n) 
       hipLaunchKernelGGL(k_test_coop_timing, dim3(1), dim3(64), 0, 0, din, dout);
     else if (op == TOP_COOP_INV)
       hipLaunchKernelGGL(k_test_coop_inv, dim3((uint32_t)((n + 3) / 4)), dim3(64), 0, 0, din, dout, (uint32_t)n);
+    else if (op == TOP_COOP_MUL_DIGITS)
+      hipLaunchKernelGGL(k_test_coop_mul_digits, rows4, dim3(64), 0, 0, din, dout, (uint32_t)n);
+    else if (op == TOP_COOP_MUL_WORDS)
+      hipLaunchKernelGGL(k_test_coop_mul_words, rows4, dim3(64), 0, 0, din, dout, (uint32_t)n);
+    else if (op == TOP_COOP_TO_FP)
+      hipLaunchKernelGGL(k_test_coop_to_fp, dim3((uint32_t)((n + 63) / 64)), dim3(64), 0, 0, din, dout, (uint32_t)n);
+    else if (op == TOP_COOP_REDUCE)
+      hipLaunchKernelGGL(k_test_coop_reduce, rows4, dim3(64), 0, 0, din, dout, (uint32_t)n);
+    else if (op == TOP_COOP_INV_RAW)
+      hipLaunchKernelGGL(k_test_coop_inv_raw, rows4, dim3(64), 0, 0, din, dout, (uint32_t)n);
+    else if (op == TOP_COOP_INV_U)
+      hipLaunchKernelGGL(k_test_coop_inv_u, dim3((uint32_t)n), dim3(64), 0, 0, din, dout);
+    else if (op == TOP_COOP_POINT_G1)
+      hipLaunchKernelGGL(k_test_cpoint_g1, rows4, dim3(64), 0, 0, din, dout, (uint32_t)n);
+    else if (op == TOP_COOP_POINT_G2)
+      hipLaunchKernelGGL(k_test_cpoint_g2, rows4, dim3(64), 0, 0, din, dout, (uint32_t)n);
     else if (op == TOP_CLEAR_COF_PROG)
       hipLaunchKernelGGL(k_test_clear_cof_prog, dim3((uint32_t)n), dim3(64), 0, 0, din, dout);
     else if (test_op_in_a(op))
