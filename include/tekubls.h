@@ -180,6 +180,53 @@ int tbls_batch_verify_idx(const tbls_set_idx* sets, size_t n, const uint64_t* ra
  * (= tbls_verify_each on one device). */
 int tbls_fast_aggregate_verify_many(const tbls_set* sets, size_t n, int* ok_per_set);
 
+/* tbls_fast_aggregate_verify_many with keys from the table (BLS.java:185-207
+ * over keys looked up by validator index, BeaconStateAccessors.java:78-97;
+ * aggregation as BlstPublicKey.aggregate, BlstPublicKey.java:55-71): no key
+ * bytes travel and no key is decompressed.  An empty key list gives 0; a set
+ * naming an invalid table key gives 0; an index >= tbls_pk_table_size(), or no
+ * table, -> TBLS_BAD_ARGUMENT.  One device. */
+int tbls_fast_aggregate_verify_many_idx(const tbls_set_idx* sets, size_t n, int* ok_per_set);
+
+/* ---- resident sync committees ----
+ * A sync committee is one fixed list of validator indices for a whole period
+ * (256 epochs; the same validator may appear more than once), and every
+ * SyncAggregate carries a participation bitvector over it.  The reference
+ * walks the committee, tests each bit and gathers the participants' keys
+ * (BlockProcessorAltair.processSyncAggregate, BlockProcessorAltair.java:
+ * 234-267) for BLS.fastAggregateVerify (BLS.java:185-207).
+ * tbls_committee_load stores the index list in `slot` on every device beside
+ * its key table, with the mask of members whose table key is invalid and the
+ * sum of the valid members' keys (BlstPublicKey.aggregate,
+ * BlstPublicKey.java:55-71), so that a nearly full set costs the few absent
+ * keys.  Loading a slot replaces it; tbls_pk_table_load empties every slot.
+ * TBLS_BAD_ARGUMENT: slot >= TBLS_COMMITTEE_SLOTS, size == 0 or
+ * > TBLS_COMMITTEE_MAX, no table, an index >= tbls_pk_table_size(). */
+#define TBLS_COMMITTEE_SLOTS 4
+#define TBLS_COMMITTEE_MAX 2048
+int tbls_committee_load(uint32_t slot, const uint32_t* key_idx, uint32_t size);
+uint32_t tbls_committee_size(uint32_t slot); /* 0: empty slot */
+
+/* One SyncAggregate-shaped set: bits is an SSZ bitvector of (size + 7) / 8
+ * bytes over the committee; member i participates iff
+ * (bits[i / 8] >> (i % 8)) & 1. */
+typedef struct {
+  const uint8_t* bits;
+  const uint8_t* msg;
+  uint32_t msg_len;
+  const uint8_t* sig;
+} tbls_set_bits;
+
+/* ok_per_set[s] = BLS.fastAggregateVerify(participants' keys in committee
+ * order, msg, sig) (BlockProcessorAltair.java:234-267, BLS.java:185-207,
+ * BlstPublicKey.java:55-71): no participant gives 0, a participating member
+ * with an invalid key gives 0 (an absent one does not matter), an aggregate
+ * key equal to infinity gives 0.  A set bit at a position >= size, or an empty
+ * slot, -> TBLS_BAD_ARGUMENT.  One device.  (eth2FastAggregateVerify's special
+ * case -- no participants with the infinity signature is true -- sits above
+ * BLS.fastAggregateVerify in the reference and stays with the caller.) */
+int tbls_fast_aggregate_verify_many_bits(uint32_t slot, const tbls_set_bits* sets, size_t n, int* ok_per_set);
+
 /* Per-set verdicts of a whole batch in one pass:
  * ok_per_set[i] = BLS.fastAggregateVerify(sets[i]) (BLS.java:185-207).
  * Replaces the recursive halving + per-task SIMPLE.verify fallback of

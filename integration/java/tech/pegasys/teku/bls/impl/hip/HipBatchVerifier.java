@@ -73,4 +73,68 @@ public final class HipBatchVerifier {
     }
     return ok[0] == 1;
   }
+
+  /*
+   * Makes `validatorIndices` (indices into the resident key table, duplicates
+   * allowed) the committee of `slot` (0..3) on every device.  A node loads the
+   * current and the next sync committee into two slots at each period boundary.
+   */
+  public static void loadCommittee(final int slot, final int[] validatorIndices) {
+    final int rc = TekuBlsHipCommittee.committeeLoad(slot, validatorIndices);
+    if (rc == TekuBlsHip.BAD_ARGUMENT) {
+      throw new IllegalArgumentException("Committee slot, size or validator index out of range, or no key table");
+    }
+    if (rc != TekuBlsHip.SUCCESS) {
+      throw new BlsException("GPU BLS backend: committeeLoad failed, code " + rc);
+    }
+  }
+
+  /*
+   * BLS.fastAggregateVerify(participants' keys, message, signature) per set
+   * (BLS.java:185-207) for sets given as the SyncAggregate participation
+   * bitvectors over the committee of committeeSize members in `slot`
+   * (BlockProcessorAltair.java:234-267): bitvectors.get(i) has
+   * (committeeSize + 7) / 8 bytes, member k participates iff bit k % 8 of byte
+   * k / 8 is set.  A set without participants is false: the caller keeps
+   * eth2FastAggregateVerify's infinity-signature case.
+   */
+  public static boolean[] fastAggregateVerifyCommittee(final int slot, final int committeeSize, final List<Bytes> bitvectors,
+                                                       final List<Bytes> messages, final List<BLSSignature> signatures) {
+    final int n = bitvectors.size();
+    final int row = (committeeSize + 7) / 8;
+    if (messages.size() != n || signatures.size() != n) {
+      throw new IllegalArgumentException("Different collection sizes");
+    }
+    int m = 0;
+    for (int i = 0; i < n; i++) {
+      if (bitvectors.get(i).size() != row) {
+        throw new IllegalArgumentException("Bitvector length does not match the committee");
+      }
+      m += messages.get(i).size();
+    }
+    final byte[] bits = new byte[row * n];
+    final byte[] msgs = new byte[m];
+    final int[] msgOff = new int[n + 1];
+    final byte[] sigs = new byte[96 * n];
+    for (int i = 0; i < n; i++) {
+      System.arraycopy(bitvectors.get(i).toArrayUnsafe(), 0, bits, row * i, row);
+      final byte[] msg = messages.get(i).toArrayUnsafe();
+      System.arraycopy(msg, 0, msgs, msgOff[i], msg.length);
+      msgOff[i + 1] = msgOff[i] + msg.length;
+      System.arraycopy(signatures.get(i).toBytesCompressed().toArrayUnsafe(), 0, sigs, 96 * i, 96);
+    }
+    final int[] each = new int[n];
+    final int rc = TekuBlsHipCommittee.fastAggregateVerifyManyBits(slot, committeeSize, bits, msgs, msgOff, sigs, each);
+    if (rc == TekuBlsHip.BAD_ARGUMENT) {
+      throw new IllegalArgumentException("Empty or reloaded committee slot, or a set bit past the committee");
+    }
+    if (rc != TekuBlsHip.SUCCESS) {
+      throw new BlsException("GPU BLS backend: fastAggregateVerifyManyBits failed, code " + rc);
+    }
+    final boolean[] ok = new boolean[n];
+    for (int i = 0; i < n; i++) {
+      ok[i] = each[i] == 1;
+    }
+    return ok;
+  }
 }

@@ -546,6 +546,78 @@ class ValidatorKeyTable:
         native.check(rc, "tbls_batch_verify_idx")
         return ok.value == 1
 
+    def fast_aggregate_verify_many(self, sets) -> List[bool]:
+        """BLS.fastAggregateVerify per set (BLS.java:185-207) over
+        [(key_indices, msg, sig96)]: the verdicts of fast_aggregate_verify_many
+        with the keys' bytes.  An empty key list gives False; an index past the
+        table raises ValueError."""
+        n = len(sets)
+        arr = (native.TblsSetIdx * max(1, n))()
+        keep = []
+        for i, (idx, msg, sig) in enumerate(sets):
+            ib = (ctypes.c_uint32 * max(1, len(idx)))(*idx)
+            mb, sb = _buf(msg), _buf(sig)
+            keep += [ib, mb, sb]
+            arr[i].key_idx = ctypes.cast(ib, ctypes.c_void_p)
+            arr[i].n_pks = len(idx)
+            arr[i].msg = ctypes.cast(mb, ctypes.c_void_p)
+            arr[i].msg_len = len(msg)
+            arr[i].sig = ctypes.cast(sb, ctypes.c_void_p)
+        out = (ctypes.c_int * max(1, n))()
+        rc = native.lib().tbls_fast_aggregate_verify_many_idx(arr, n, out)
+        if rc == native.BAD_ARGUMENT:
+            raise ValueError("key index out of range / no key table")
+        native.check(rc, "tbls_fast_aggregate_verify_many_idx")
+        return [bool(out[i]) for i in range(n)]
+
+    def load_committee(self, slot, indices) -> "Committee":
+        """Make the committee `indices` (validator indices into this table,
+        duplicates allowed) resident in `slot` on every device."""
+        return Committee(slot, indices)
+
+
+class Committee:
+    """A resident sync committee (C ABI tbls_committee_load /
+    tbls_fast_aggregate_verify_many_bits): the index list stays on the devices
+    for its period, and each SyncAggregate names its participants by the
+    512-bit vector it carries (BlockProcessorAltair.java:234-267).  Loading a
+    key table empties every slot."""
+
+    def __init__(self, slot, indices):
+        idx = list(indices)
+        arr = (ctypes.c_uint32 * max(1, len(idx)))(*idx) if all(0 <= i < 2**32 for i in idx) else None
+        rc = native.BAD_ARGUMENT if arr is None or not 0 <= slot < 2**32 else native.lib().tbls_committee_load(slot, arr, len(idx))
+        if rc == native.BAD_ARGUMENT:
+            raise ValueError("committee slot, size or key index out of range / no key table")
+        native.check(rc, "tbls_committee_load")
+        self.slot = slot
+        self.size = len(idx)
+
+    def fast_aggregate_verify_many(self, sets) -> List[bool]:
+        """BLS.fastAggregateVerify per set over [(bits_bytes, msg, sig96)]:
+        bits_bytes is the SSZ bitvector of (size + 7) // 8 bytes, member i
+        participates iff (bits[i // 8] >> (i % 8)) & 1.  No participant gives
+        False; a set bit past the committee raises ValueError."""
+        n = len(sets)
+        nb = (self.size + 7) // 8
+        arr = (native.TblsSetBits * max(1, n))()
+        keep = []
+        for i, (bits, msg, sig) in enumerate(sets):
+            if len(bits) != nb:
+                raise ValueError("bitvector length does not match the committee")
+            bb, mb, sb = _buf(bits), _buf(msg), _buf(sig)
+            keep += [bb, mb, sb]
+            arr[i].bits = ctypes.cast(bb, ctypes.c_void_p)
+            arr[i].msg = ctypes.cast(mb, ctypes.c_void_p)
+            arr[i].msg_len = len(msg)
+            arr[i].sig = ctypes.cast(sb, ctypes.c_void_p)
+        out = (ctypes.c_int * max(1, n))()
+        rc = native.lib().tbls_fast_aggregate_verify_many_bits(self.slot, arr, n, out)
+        if rc == native.BAD_ARGUMENT:
+            raise ValueError("empty committee slot / a set bit past the committee")
+        native.check(rc, "tbls_fast_aggregate_verify_many_bits")
+        return [bool(out[i]) for i in range(n)]
+
 
 def _as_pk(pk) -> HipPublicKey:
     if isinstance(pk, HipPublicKey):

@@ -418,6 +418,112 @@ __device__ TB_INLINE void ka_affine(const coop::cj1& t, int32_t (*zb)[16], fp& i
   crow::to_fp_n<2>(v2, zb, out);
 }
 
+// The tail the multi-key kernels share (all threads call, after the row tree):
+// row 0 of S.pt / S.inf holds the set's aggregate, S.bad an invalid key's
+// code.  Z = 0 or infinity sends the set to gen(r, o), the caller's exact
+// one-lane body; otherwise P[i] = [rnd] apk by nibbles, and P2[i] = -[r] g1
+// (when P2 is given) on row 16; failures go to set_code / n_bad.
+template <class GEN>
+__device__ TB_INLINE void ka_finish(ka_set& S, uint32_t i, uint64_t rnd, const uint64_t* __restrict__ rand, g1a* __restrict__ P,
+                                    g1a* __restrict__ P2, uint8_t* __restrict__ set_code, uint32_t* __restrict__ n_bad,
+                                    const g1a* __restrict__ comb, int q, int d, const coop::cctx& K, const c32& one, const GEN& gen) {
+  // ---- the aggregate: exceptional / infinite -> one-lane body; invalid key or r = 0 -> fail
+  if (q == 0) {
+    const c32 zv[1] = {S.pt[0][2][d]};
+    const bool zero = S.inf[0] != 0 || crow::zeros_n<1>(zv, S.zb[0]) != 0u;
+    if (d == 0) {
+      int mode = 0;
+      if (S.bad != TB_SUCCESS) {
+        mode = 2;
+      } else if (zero) {
+        mode = 1;
+      } else if (rnd == 0) {
+        S.bad = TB_PK_IS_INFINITY;  // [0] apk (stage_set_pk_finish)
+        mode = 2;
+      }
+      S.mode = mode;
+    }
+  }
+  __syncthreads();
+  const int mode = S.mode;
+  // ---- row 16: -[r] g1 (one mixed addition per nonzero byte of r: neg_r_g1)
+  if (q == 16 && P2) {
+    const uint64_t rr = rand[i];
+    coop::cj1 cacc = {one, one, c32(0)};
+    bool cinf = true;
+    for (int k = 0; k < 8; k++) {
+      const uint32_t dg = (uint32_t)(rr >> (8 * k)) & 255u;
+      if (dg) {
+        const g1a* cq = comb + k * 256 + dg;
+        const c32 qx = crow::from_fp(cq->x), qy = crow::from_fp(cq->y);
+        if (cinf) {
+          cacc = {qx, qy, one};
+          cinf = false;
+        } else {
+          cacc = coop::madd(cacc, qx, qy, K);
+        }
+      }
+    }
+    if (!cinf) ka_affine(cacc, S.zb[1], S.inv[1], S.out[1], d, K);
+    if (d == 0) {
+      g1a o;
+      o.x = cinf ? fp_zero() : S.out[1][0];
+      o.y = fp_neg(cinf ? fp_zero() : S.out[1][1]);
+      P2[i] = o;
+    }
+  }
+  // ---- [r] apk by nibbles on rows 0..15
+  coop::cj1 t = {c32(0), c32(0), c32(0)};
+  bool tinf = true;
+  if (mode == 0 && q < 16) {
+    const uint32_t nib = (uint32_t)(rnd >> (4 * q)) & 15u;
+    if (nib) {
+      coop::cj1 a = {S.pt[0][0][d], S.pt[0][1][d], S.pt[0][2][d]};
+      for (int k = 0; k < 4 * q; k++) a = coop::dbl(a, K);  // 2^(4q) apk
+      t = a;
+      for (int bit = 31 - __builtin_clz(nib) - 1; bit >= 0; --bit) {
+        t = coop::dbl(t, K);
+        if ((nib >> bit) & 1u) t = coop::add(t, a, K);
+      }
+      tinf = false;
+    }
+  }
+  __syncthreads();  // every row has read the aggregate
+  if (mode == 0 && q < 16) {
+    S.pt[q][0][d] = t.x;
+    S.pt[q][1][d] = t.y;
+    S.pt[q][2][d] = t.z;
+    if (d == 0) S.inf[q] = tinf ? 1u : 0u;
+  }
+  __syncthreads();
+  if (mode == 0) ka_tree(S, 16, q, d, K);
+  if (q == 0) {
+    int code = S.bad;
+    if (mode == 0) {
+      const coop::cj1 rp = {S.pt[0][0][d], S.pt[0][1][d], S.pt[0][2][d]};
+      ka_affine(rp, S.zb[0], S.inv[0], S.out[0], d, K);
+    } else if (mode == 1 && d == 0) {  // infinity or an exceptional addition: the exact one-lane body
+      g1a o;
+      code = gen(rnd, o);
+      S.out[0][0] = o.x;
+      S.out[0][1] = o.y;
+    }
+    if (d == 0) {  // lane 0's code is the set's in every mode
+      g1a o;
+      o.x = fp_zero();
+      o.y = fp_zero();
+      if (code == TB_SUCCESS) {
+        o.x = S.out[0][0];
+        o.y = S.out[0][1];
+      } else {
+        set_code[i] = (uint8_t)code;
+        atomicAdd(n_bad, 1u);
+      }
+      P[i] = o;
+    }
+  }
+}
+
 extern "C" __global__ void __launch_bounds__(KA_ROWS * 16)
     k_set_pk_agg_coop(const uint32_t* __restrict__ pk_off, const g1a* __restrict__ pk_aff, const uint8_t* __restrict__ pk_code,
                       const uint64_t* __restrict__ rand, const uint32_t* __restrict__ list, const uint32_t* __restrict__ cnt,
@@ -460,101 +566,161 @@ extern "C" __global__ void __launch_bounds__(KA_ROWS * 16)
     if (d == 0) S.inf[q] = inf ? 1u : 0u;
     __syncthreads();
     ka_tree(S, KA_ROWS, q, d, K);
-    // ---- the aggregate: exceptional / infinite -> one-lane body; invalid key or r = 0 -> fail
-    if (q == 0) {
-      const c32 zv[1] = {S.pt[0][2][d]};
-      const bool zero = S.inf[0] != 0 || crow::zeros_n<1>(zv, S.zb[0]) != 0u;
-      if (d == 0) {
-        int mode = 0;
-        if (S.bad != TB_SUCCESS) {
-          mode = 2;
-        } else if (zero) {
-          mode = 1;
-        } else if (rnd == 0) {
-          S.bad = TB_PK_IS_INFINITY;  // [0] apk (stage_set_pk_finish)
-          mode = 2;
-        }
-        S.mode = mode;
-      }
+    ka_finish(S, i, rnd, rand, P, P2, set_code, n_bad, comb, q, d, K, one, [&](uint64_t r, g1a& o) {
+      return ka_set_generic(pk_aff, pk_code, b, e, r, o, key_idx, tab_n);
+    });
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Sync-committee sets from a resident committee and a participation bitfield
+// (BlockProcessorAltair.java:234-267: the committee's keys whose bit is set,
+// in committee order, to BLS.fastAggregateVerify, BLS.java:185-207).  The
+// committee is a list of table indices (members), its bad-member mask and the
+// affine sum of its valid members (k_committee_mask + one set of this kernel
+// at load time).  One 512-thread workgroup per set, the layout and outputs of
+// k_set_pk_agg_coop:
+//   * the set's bit row is staged in LDS (at most 256 B), its participants
+//     (c) and absent valid members (a) counted, and ANDed with the bad-member
+//     mask: a participating invalid member fails the set (PK_IS_INFINITY);
+//   * a < c with a usable committee sum: the rows walk the ABSENT valid
+//     members and add their negations, the row tree meets them and row 0 adds
+//     the committee sum (near-full participation: a handful of additions
+//     instead of ~500); otherwise the rows walk the participants.  Row q owns
+//     members q, q + 32, ...: bit q of each word of the row, so the walk is
+//     row-uniform;
+//   * an exceptional addition on either side (duplicate members make P == +-Q
+//     ordinary) leaves Z = 0, and ka_finish then sums the PARTICIPANTS on one
+//     lane with the exact formulas -- never a one-lane complement; a sum that
+//     is truly infinity fails the set.
+// ---------------------------------------------------------------------------
+#define KB_WORDS 64  // 2048 members
+struct kb_set {
+  ka_set a;
+  uint32_t row[KB_WORDS];  // the bit row, then the walk mask
+  uint32_t c, av, hit;
+};
+
+// bad[t]: bit j set when member 32 t + j's table key is not TB_SUCCESS (or its
+// index is past the table); valid[t]: the in-range members that are not bad
+extern "C" __global__ void __launch_bounds__(KB_WORDS)
+    k_committee_mask(const uint32_t* __restrict__ members, uint32_t size, const uint8_t* __restrict__ tab_code, uint32_t tab_n,
+                     uint32_t* __restrict__ bad, uint32_t* __restrict__ valid) {
+  const uint32_t t = threadIdx.x;
+  if (t >= KB_WORDS) return;
+  uint32_t b = 0, in = 0;
+  for (uint32_t j = 0; j < 32; j++) {
+    const uint32_t m = 32 * t + j;
+    if (m >= size) break;
+    in |= 1u << j;
+    const uint32_t k = members[m];
+    if (k >= tab_n || tab_code[k] != TB_SUCCESS) b |= 1u << j;
+  }
+  bad[t] = b;
+  valid[t] = in & ~b;
+}
+
+// the exact one-lane body of a bitfield set: the participants, in committee order
+__device__ TB_NOINLINE int kb_set_generic(const uint32_t* row, const uint32_t* members, uint32_t size, const g1a* tab_aff,
+                                          const uint8_t* tab_code, uint32_t tab_n, uint64_t r, g1a& o) {
+  o.x = fp_zero();
+  o.y = fp_zero();
+  g1j acc = jac_inf<fp>();
+  for (uint32_t j = 0; j < size; j++) {
+    if (!((row[j >> 5] >> (j & 31u)) & 1u)) continue;
+    const uint32_t k = members[j];
+    if (k >= tab_n) return TB_BAD_ENCODING;
+    if (tab_code[k] != TB_SUCCESS) return TB_PK_IS_INFINITY;  // BlstPublicKey.java:58-65
+    acc = jac_add_aff(acc, tab_aff[k]);
+  }
+  return stage_set_pk_finish(acc, r, o);
+}
+
+// rows: n bit rows of stride_w words (>= ceil(size / 32); bits past size are
+// ignored); csum / sum_ok: the committee sum and whether it may be used.
+extern "C" __global__ void __launch_bounds__(KA_ROWS * 16)
+    k_set_pk_bits_coop(const uint32_t* __restrict__ rows, uint32_t stride_w, const uint32_t* __restrict__ members, uint32_t size,
+                       const uint32_t* __restrict__ bad, const g1a* __restrict__ csum, uint32_t sum_ok,
+                       const g1a* __restrict__ tab_aff, const uint8_t* __restrict__ tab_code, uint32_t tab_n,
+                       const uint64_t* __restrict__ rand, uint32_t n, g1a* __restrict__ P, uint8_t* __restrict__ set_code,
+                       uint32_t* __restrict__ n_bad, g1a* __restrict__ P2, const g1a* __restrict__ comb, uint32_t unit_r) {
+  __shared__ kb_set B;
+  ka_set& S = B.a;
+  tb_latency_prio();
+  const int q = crow::row(), d = crow::dig();
+  const coop::cctx K = coop::cctx_load();
+  const c32 one = crow::from_const(R1);
+  if (size > 32u * KB_WORDS) size = 32u * KB_WORDS;
+  const uint32_t nw = std::min<uint32_t>((size + 31u) / 32u, stride_w);
+  for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
+    const uint32_t* row = rows + (size_t)i * stride_w;
+    const uint64_t rnd = unit_r ? 1ull : rand[i];
+    if (threadIdx.x == 0) {
+      S.bad = TB_SUCCESS;
+      B.c = B.av = B.hit = 0u;
     }
     __syncthreads();
-    const int mode = S.mode;
-    // ---- row 16: -[r] g1 (one mixed addition per nonzero byte of r: neg_r_g1)
-    if (q == 16 && P2) {
-      const uint64_t rr = rand[i];
-      coop::cj1 cacc = {one, one, c32(0)};
-      bool cinf = true;
-      for (int k = 0; k < 8; k++) {
-        const uint32_t dg = (uint32_t)(rr >> (8 * k)) & 255u;
-        if (dg) {
-          const g1a* cq = comb + k * 256 + dg;
-          const c32 qx = crow::from_fp(cq->x), qy = crow::from_fp(cq->y);
-          if (cinf) {
-            cacc = {qx, qy, one};
-            cinf = false;
-          } else {
-            cacc = coop::madd(cacc, qx, qy, K);
-          }
-        }
-      }
-      if (!cinf) ka_affine(cacc, S.zb[1], S.inv[1], S.out[1], d, K);
-      if (d == 0) {
-        g1a o;
-        o.x = cinf ? fp_zero() : S.out[1][0];
-        o.y = fp_neg(cinf ? fp_zero() : S.out[1][1]);
-        P2[i] = o;
-      }
-    }
-    // ---- [r] apk by nibbles on rows 0..15
-    coop::cj1 t = {c32(0), c32(0), c32(0)};
-    bool tinf = true;
-    if (mode == 0 && q < 16) {
-      const uint32_t nib = (uint32_t)(rnd >> (4 * q)) & 15u;
-      if (nib) {
-        coop::cj1 a = {S.pt[0][0][d], S.pt[0][1][d], S.pt[0][2][d]};
-        for (int k = 0; k < 4 * q; k++) a = coop::dbl(a, K);  // 2^(4q) apk
-        t = a;
-        for (int bit = 31 - __builtin_clz(nib) - 1; bit >= 0; --bit) {
-          t = coop::dbl(t, K);
-          if ((nib >> bit) & 1u) t = coop::add(t, a, K);
-        }
-        tinf = false;
-      }
-    }
-    __syncthreads();  // every row has read the aggregate
-    if (mode == 0 && q < 16) {
-      S.pt[q][0][d] = t.x;
-      S.pt[q][1][d] = t.y;
-      S.pt[q][2][d] = t.z;
-      if (d == 0) S.inf[q] = tinf ? 1u : 0u;
+    // ---- the bit row: participants, absent valid members, participating bad members
+    uint32_t wb = 0, wa = 0;
+    if (threadIdx.x < nw) {
+      const uint32_t t = threadIdx.x, left = size - 32u * t;
+      const uint32_t in = left >= 32u ? 0xffffffffu : (1u << left) - 1u, bd = bad[t];
+      wb = row[t] & in;
+      wa = ~wb & ~bd & in;
+      atomicAdd(&B.c, (uint32_t)__popc(wb));
+      atomicAdd(&B.av, (uint32_t)__popc(wa));
+      if (wb & bd) atomicOr(&B.hit, 1u);
+      wb &= ~bd;
     }
     __syncthreads();
-    if (mode == 0) ka_tree(S, 16, q, d, K);
-    if (q == 0) {
-      int code = S.bad;
-      if (mode == 0) {
-        const coop::cj1 rp = {S.pt[0][0][d], S.pt[0][1][d], S.pt[0][2][d]};
-        ka_affine(rp, S.zb[0], S.inv[0], S.out[0], d, K);
-      } else if (mode == 1 && d == 0) {  // infinity or an exceptional addition: the exact one-lane body
-        g1a o;
-        code = ka_set_generic(pk_aff, pk_code, b, e, rnd, o, key_idx, tab_n);
-        S.out[0][0] = o.x;
-        S.out[0][1] = o.y;
+    const bool comp = sum_ok != 0u && B.av < B.c;  // the cheaper side
+    if (threadIdx.x < nw) B.row[threadIdx.x] = comp ? wa : wb;
+    if (threadIdx.x == 0 && B.hit) S.bad = TB_PK_IS_INFINITY;  // BlstPublicKey.java:58-65
+    __syncthreads();
+    // ---- row sums over the chosen side (row-uniform: bit q of every word)
+    coop::cj1 acc = {c32(0), c32(0), c32(0)};
+    bool inf = true;
+    for (uint32_t t = 0; t < nw; t++) {
+      if (!((B.row[t] >> q) & 1u)) continue;
+      const uint32_t k = members[32u * t + (uint32_t)q];
+      if (k >= tab_n) {
+        S.bad = TB_BAD_ENCODING;
+        continue;
       }
-      if (d == 0) {  // lane 0's code is the set's in every mode
-        g1a o;
-        o.x = fp_zero();
-        o.y = fp_zero();
-        if (code == TB_SUCCESS) {
-          o.x = S.out[0][0];
-          o.y = S.out[0][1];
-        } else {
-          set_code[i] = (uint8_t)code;
-          atomicAdd(n_bad, 1u);
-        }
-        P[i] = o;
+      const c32 qx = crow::from_fp(tab_aff[k].x), y = crow::from_fp(tab_aff[k].y);
+      const c32 qy = comp ? -y : y;
+      if (inf) {
+        acc = {qx, qy, one};
+        inf = false;
+      } else {
+        acc = coop::madd(acc, qx, qy, K);
       }
     }
+    S.pt[q][0][d] = acc.x;
+    S.pt[q][1][d] = acc.y;
+    S.pt[q][2][d] = acc.z;
+    if (d == 0) S.inf[q] = inf ? 1u : 0u;
+    __syncthreads();
+    ka_tree(S, KA_ROWS, q, d, K);
+    if (comp && q == 0) {  // the committee sum minus the absent members
+      const c32 sx = crow::from_fp(csum->x), sy = crow::from_fp(csum->y);
+      coop::cj1 m = {sx, sy, one};
+      if (S.inf[0] == 0) {
+        const coop::cj1 neg = {S.pt[0][0][d], S.pt[0][1][d], S.pt[0][2][d]};
+        m = coop::madd(neg, sx, sy, K);
+      }
+      __builtin_amdgcn_wave_barrier();  // every lane of the row has read inf[0]
+      S.pt[0][0][d] = m.x;
+      S.pt[0][1][d] = m.y;
+      S.pt[0][2][d] = m.z;
+      if (d == 0) S.inf[0] = 0u;
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    }
+    ka_finish(S, i, rnd, rand, P, P2, set_code, n_bad, comb, q, d, K, one, [&](uint64_t r, g1a& o) {
+      return kb_set_generic(row, members, size, tab_aff, tab_code, tab_n, r, o);
+    });
     __syncthreads();
   }
 }

@@ -111,3 +111,6 @@ inline void tb_launch_final_recs(const uint8_t* recs, uint32_t g, hipStream_t s,
   else
     hipLaunchKernelGGL(k_final_verify_recs, dim3(1), dim3(64), 0, s, recs, g, result);
 }
+// resident committees (k_kcoop.hip): the bad-member mask, and [r] apk of sets given as participation bit rows
+extern "C" __global__ void k_committee_mask(const uint32_t* __restrict__ members, uint32_t size, const uint8_t* __restrict__ tab_code, uint32_t tab_n, uint32_t* __restrict__ bad, uint32_t* __restrict__ valid);
+extern "C" __global__ void k_set_pk_bits_coop(const uint32_t* __restrict__ rows, uint32_t stride_w, const uint32_t* __restrict__ members, uint32_t size, const uint32_t* __restrict__ bad, const g1a* __restrict__ csum, uint32_t sum_ok, const g1a* __restrict__ tab_aff, const uint8_t* __restrict__ tab_code, uint32_t tab_n, const uint64_t* __restrict__ rand, uint32_t n, g1a* __restrict__ P, uint8_t* __restrict__ set_code, uint32_t* __restrict__ n_bad, g1a* __restrict__ P2, const g1a* __restrict__ comb, uint32_t unit_r);

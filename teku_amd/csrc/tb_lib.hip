@@ -90,6 +90,11 @@ struct dev_ctx {
   hipStream_t aux[3] = {nullptr, nullptr, nullptr};  // concurrent per-set stages (aux[1] signatures + bucket sums, aux[2] hash_to_G2: high priority)
   dbuf tab_aff, tab_code;                    // device-resident public-key table (tbls_pk_table_load)
   uint32_t tab_n = 0;
+  // resident committees (tbls_committee_load): per slot TB_CM_STRIDE bytes of
+  // cmt (members, bad-member mask, valid-member row, the valid members' sum,
+  // the load pass's code and failure count); size 0: empty slot
+  dbuf cmt;
+  uint32_t cm_size[TBLS_COMMITTEE_SLOTS] = {0, 0, 0, 0}, cm_sum_ok[TBLS_COMMITTEE_SLOTS] = {0, 0, 0, 0};
   hipEvent_t e_fork = nullptr, e_join[3] = {nullptr, nullptr, nullptr}, e_sig = nullptr;
   hipEvent_t e_t0 = nullptr, e_t1 = nullptr;  // per-call device timing (shard_launch), created once
   // Last use of `ws` on any stream.  The device-resident API queues work on the
@@ -541,6 +546,36 @@ void launch_set_pk(hipStream_t s, uint32_t n, uint32_t n_entries, const uint32_t
                        (const uint32_t*)mlist, (const uint32_t*)mcnt, P, set_code, n_bad, key_idx, tab_n);
 }
 
+// A resident committee on one device (dev_ctx::cmt) and the bit rows' stride.
+#define TB_CM_WORDS (TBLS_COMMITTEE_MAX / 32)
+#define TB_CM_OFF_BAD ((size_t)TBLS_COMMITTEE_MAX * 4)
+#define TB_CM_OFF_VALID (TB_CM_OFF_BAD + 256)
+#define TB_CM_OFF_SUM (TB_CM_OFF_VALID + 256)
+#define TB_CM_OFF_CODE (TB_CM_OFF_SUM + 256)
+#define TB_CM_STRIDE (TB_CM_OFF_CODE + 256)
+struct bits_src {
+  const uint32_t *members, *bad;
+  const g1a* sum;
+  uint32_t size, sum_ok, stride_w;
+};
+inline uint32_t bits_stride_w(uint32_t size) { return (size + 31u) / 32u; }  // the (size + 7) / 8 bytes, rounded to 4
+inline bits_src committee_src(const dev_ctx& c, uint32_t slot) {
+  const uint8_t* m = c.cmt.as<const uint8_t>((size_t)slot * TB_CM_STRIDE);
+  return {(const uint32_t*)m, (const uint32_t*)(m + TB_CM_OFF_BAD), (const g1a*)(m + TB_CM_OFF_SUM), c.cm_size[slot], c.cm_sum_ok[slot],
+          bits_stride_w(c.cm_size[slot])};
+}
+
+// launch_set_pk for sets given as participation bit rows over a resident
+// committee (rows: n rows of cm.stride_w words): one kernel, every set on the
+// lane-cooperative rows (k_set_pk_bits_coop), keys from the table.  unit_r: r = 1.
+void launch_set_pk_bits(hipStream_t s, uint32_t n, const uint32_t* rows, const bits_src& cm, const g1a* aff, const uint8_t* code,
+                        uint32_t tab_n, const uint64_t* rand, g1a* P, uint8_t* set_code, uint32_t* n_bad, g1a* P2, const g1a* comb,
+                        uint32_t unit_r) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_set_pk_bits_coop, dim3(std::min<uint32_t>(n, 4096u)), dim3(512), 0, s, rows, cm.stride_w, cm.members, cm.size, cm.bad,
+                     cm.sum, cm.sum_ok, aff, code, tab_n, rand, n, P, set_code, n_bad, P2, comb, unit_r);
+}
+
 // k_lines.hip: the segmented accumulator with f in LDS and two lines per
 // product (tb_lines.h miller_accs_lds_body).  Measured at 131,072 sets
 // (profiles/r05_bench_acc_lds_ab.json): Miller stage alone 13.3 -> 12.6 ms
@@ -582,7 +617,8 @@ extern "C" __global__ void k_sig_check_coop(const uint8_t* __restrict__ sigs, ui
                                             uint8_t* __restrict__ sig_code, uint32_t* __restrict__ n_bad);  // k_kcoop.hip
 int launch_partial(dev_ctx& c, const tbls_dev_batch& b, hipStream_t s, void* partial_out, ws_layout& L,
                    const uint8_t* dst, uint32_t dlen, hipEvent_t* ev = nullptr, bool serial = false,
-                   const uint32_t* key_idx = nullptr, bool settle = false) {
+                   const uint32_t* key_idx = nullptr, bool settle = false, const bits_src* cm = nullptr) {
+  // cm: the sets are bit rows over a resident committee (key_idx: the rows)
   const uint32_t n = b.n;
   const bool use_tab = key_idx != nullptr;  // keys = indices into the resident table: no decompression
   const uint32_t K = use_tab ? 0 : b.n_keys;
@@ -664,7 +700,12 @@ int launch_partial(dev_ctx& c, const tbls_dev_batch& b, hipStream_t s, void* par
   HIPCHK(hipEventRecord(c.e_join[1], sb));
   // --- stream a: public keys, [r] apk (+ -[r] g1 for the signature pairs) -----
   TB_EV(0, sa);
-  if (b.n_keys == n && n && n <= TB_HASH_WAVE_MAX && coop()) {
+  if (cm) {
+    TB_EV(1, sa);
+    TB_EV(2, sa);
+    launch_set_pk_bits(sa, n, key_idx, *cm, c.tab_aff.as<const g1a>(), c.tab_code.as<const uint8_t>(), c.tab_n, b.rand, P, w + L.set_code,
+                       (uint32_t*)(w + L.n_bad), pp.msm ? nullptr : P + n, c.comb.as<const g1a>(), 0u);
+  } else if (b.n_keys == n && n && n <= TB_HASH_WAVE_MAX && coop()) {
     // one kernel: decode + G1 check (wave 0) beside -[r] g1, then [r] pk (wave
     // 1); its time shows as stage 0.  As many keys as sets: one key per set
     // in every real batch (a set of several keys beside empty ones still
@@ -866,12 +907,51 @@ struct packed {
 };
 
 // keys of a set: 48-byte encodings (tbls_set) or 4-byte table indices (tbls_set_idx)
+// A bitfield set inside the library: n_pks is its row in the key area, in
+// 4-byte words (the stride of every row of the call); size: the committee's
+// size the caller saw (checked again under the device lock).
+struct set_bits_i {
+  const uint8_t* bits;
+  uint32_t n_pks;
+  const uint8_t* msg;
+  uint32_t msg_len;
+  const uint8_t* sig;
+  uint32_t slot, size;
+};
 inline const void* set_keys(const tbls_set& s) { return s.pks; }
 inline const void* set_keys(const tbls_set_idx& s) { return s.key_idx; }
-inline uint32_t idx_of(const tbls_set& s, uint32_t k) { return (void)s, k; }
-inline uint32_t idx_of(const tbls_set_idx& s, uint32_t k) { return s.key_idx[k]; }
 template <class SET>
 constexpr size_t key_bytes() { return std::is_same<SET, tbls_set>::value ? 48 : 4; }
+
+template <class SET>
+inline void pack_keys(uint8_t* dst, const SET& s) {
+  if (s.n_pks) memcpy(dst, set_keys(s), (size_t)s.n_pks * key_bytes<SET>());
+}
+inline void pack_keys(uint8_t* dst, const set_bits_i& s) {  // the bit row, zero-padded to its stride
+  const size_t nb = (s.size + 7u) / 8u;
+  memset(dst, 0, (size_t)s.n_pks * 4);
+  memcpy(dst, s.bits, nb);
+}
+
+// The keys of sets[lo, hi) against device c's state, under its lock (a reload
+// cannot interleave): table indices below the table's size; bit rows over a
+// loaded committee of the size the caller saw.
+template <class SET>
+int check_keys(const dev_ctx* c, const SET* sets, size_t lo, size_t hi) {
+  if constexpr (std::is_same<SET, tbls_set_idx>::value) {
+    if (!c->tab_n) return TBLS_BAD_ARGUMENT;
+    for (size_t i = lo; i < hi; i++)
+      for (uint32_t k = 0; k < sets[i].n_pks; k++)
+        if (sets[i].key_idx[k] >= c->tab_n) return TBLS_BAD_ARGUMENT;
+  } else if constexpr (std::is_same<SET, set_bits_i>::value) {
+    if (!c->tab_n) return TBLS_BAD_ARGUMENT;
+    for (size_t i = lo; i < hi; i++)
+      if (sets[i].slot >= TBLS_COMMITTEE_SLOTS || sets[i].slot != sets[lo].slot || !sets[i].size ||
+          sets[i].size != c->cm_size[sets[i].slot] || sets[i].n_pks != bits_stride_w(sets[i].size))
+        return TBLS_BAD_ARGUMENT;
+  }
+  return TBLS_SUCCESS;
+}
 
 template <class SET>
 packed pack_layout(const SET* sets, size_t lo, size_t hi, uint32_t dlen) {
@@ -906,7 +986,7 @@ void pack_fill(uint8_t* h, const packed& p, const SET* sets, size_t lo, const ui
     const SET& s = sets[lo + i];
     pkoff[i] = k;
     moff[i] = m;
-    if (s.n_pks) memcpy(h + p.off_pks + (size_t)k * key_bytes<SET>(), set_keys(s), (size_t)s.n_pks * key_bytes<SET>());
+    pack_keys(h + p.off_pks + (size_t)k * key_bytes<SET>(), s);
     if (s.msg_len) memcpy(h + p.off_msgs + m, s.msg, s.msg_len);
     memcpy(h + p.off_sigs + (size_t)i * 96, s.sig, 96);
     rr[i] = rand ? rand[lo + i] : 1;
@@ -926,14 +1006,13 @@ const uint8_t ETH2_DST[] = "BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_";
 template <class SET>
 int shard_launch(dev_ctx* c, const SET* sets, size_t lo, size_t hi, const uint64_t* rand, const uint8_t* dst, uint32_t dlen,
                  uint8_t** dpart, ws_layout& L, uint32_t* n_out, bool settle = false) {
-  constexpr bool idx_mode = !std::is_same<SET, tbls_set>::value;
+  constexpr bool idx_mode = !std::is_same<SET, tbls_set>::value;  // keys from the table: indices, or committee bit rows
+  constexpr bool bits_mode = std::is_same<SET, set_bits_i>::value;
   HIPCHK(hipSetDevice(c->dev));
-  if (idx_mode) {  // key indices against this device's table, under its lock (a reload cannot interleave)
-    if (!c->tab_n) return TBLS_BAD_ARGUMENT;
-    for (size_t i = lo; i < hi; i++)
-      for (uint32_t k = 0; k < sets[i].n_pks; k++)
-        if (idx_of(sets[i], k) >= c->tab_n) return TBLS_BAD_ARGUMENT;
-  }
+  if (const int rc = check_keys(c, sets, lo, hi)) return rc;
+  bits_src cm{};
+  if constexpr (bits_mode)
+    if (hi > lo) cm = committee_src(*c, sets[lo].slot);
   packed p = pack_layout(sets, lo, hi, dlen);
   const size_t in_total = p.total + TBLS_PARTIAL_BYTES + 256;
   hipStream_t s = c->stream;
@@ -955,7 +1034,7 @@ int shard_launch(dev_ctx* c, const SET* sets, size_t lo, size_t hi, const uint64
   *n_out = p.n;
   HIPCHK(hipEventRecord(c->e_t0, s));
   int rc = launch_partial(*c, b, s, *dpart, L, di + p.off_dst, dlen, nullptr, false, idx_mode ? (const uint32_t*)(di + p.off_pks) : nullptr,
-                          settle);
+                          settle, bits_mode ? &cm : nullptr);
   if (rc) return rc;
   HIPCHK(hipEventRecord(c->e_t1, s));
   return TBLS_SUCCESS;
@@ -1430,6 +1509,7 @@ extern "C" void tbls_shutdown(void) {
     if (c->comb.p) (void)hipFree(c->comb.p);
     if (c->tab_aff.p) (void)hipFree(c->tab_aff.p);
     if (c->tab_code.p) (void)hipFree(c->tab_code.p);
+    if (c->cmt.p) (void)hipFree(c->cmt.p);
     if (c->hin.p) (void)hipHostFree(c->hin.p);
     if (c->hout.p) (void)hipHostFree(c->hout.p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1625,6 +1705,7 @@ extern "C" int tbls_pk_table_load(const uint8_t* pks, size_t K, uint8_t* codes) 
     HIPCHK(ws_acquire(*c, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->tab_n = 0;
+    for (uint32_t& sz : c->cm_size) sz = 0;  // the committees' indices meant the old table
     if (c->in.ensure(K * 48) || c->tab_aff.ensure(K * sizeof(g1a)) || c->tab_code.ensure(K)) return TBLS_DEVICE_ERROR;
     HIPCHK(hipMemcpyAsync(c->in.p, pks, K * 48, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_pk_decompress, dim3((uint32_t)((K + TB_BLOCK - 1) / TB_BLOCK)), dim3(TB_BLOCK), 0, c->stream,
@@ -1678,12 +1759,16 @@ extern "C" int tbls_verify(const uint8_t pk[48], const uint8_t* msg, size_t len,
 // Per-set fastAggregateVerify verdicts for sets[lo, hi) on device d in one
 // pass (k_each.hip): shared per-set stages with r = 1, then one thread per set
 // for its two-pair Miller loop and final exponentiation.
-static int run_each(int d, const tbls_set* sets, size_t lo, size_t hi, uint8_t* ok_host) {
+// Keys as bytes (decompressed here), table indices or committee bit rows.
+template <class SET>
+static int run_each(int d, const SET* sets, size_t lo, size_t hi, uint8_t* ok_host) {
+  constexpr bool bytes_mode = std::is_same<SET, tbls_set>::value, bits_mode = std::is_same<SET, set_bits_i>::value;
   dev_ctx* c = ctx_for(d);
   if (!c) return TBLS_DEVICE_ERROR;
   std::lock_guard<std::mutex> lk(c->mu);
   tb::stat_add(tb::TB_STAT_EACH);
   HIPCHK(hipSetDevice(c->dev));
+  if (const int rc = check_keys(c, sets, lo, hi)) return rc;
   packed p = pack_layout(sets, lo, hi, 43);
   if (c->hin.ensure(p.total + 256) || c->in.ensure(p.total + 256)) return TBLS_DEVICE_ERROR;
   pack_fill(c->hin.b(), p, sets, lo, nullptr, ETH2_DST, 43);  // r = 1 for every set
@@ -1692,7 +1777,7 @@ static int run_each(int d, const tbls_set* sets, size_t lo, size_t hi, uint8_t* 
   HIPCHK(hipStreamSynchronize(s));  // ws may be reallocated below
   HIPCHK(hipMemcpyAsync(c->in.p, c->hin.p, p.total, hipMemcpyHostToDevice, s));
   const uint8_t* di = c->in.as<uint8_t>();
-  const uint32_t n = p.n, K = p.K;
+  const uint32_t n = p.n, K = bytes_mode ? p.K : 0u;  // keys to decompress
   size_t o = 0;
   const size_t pk_aff = o;   o = align_up(o + (size_t)K * sizeof(g1a));
   const size_t pk_code = o;  o = align_up(o + (K ? K : 1));
@@ -1714,9 +1799,17 @@ static int run_each(int d, const tbls_set* sets, size_t lo, size_t hi, uint8_t* 
   if (K)
     hipLaunchKernelGGL(k_pk_decompress, dim3((K + TB_BLOCK - 1) / TB_BLOCK), blk, 0, s, di + p.off_pks, K, (g1a*)(w + pk_aff),
                        w + pk_code);
-  launch_set_pk(s, n, K, (const uint32_t*)(di + p.off_pkoff), (const g1a*)(w + pk_aff), (const uint8_t*)(w + pk_code),
-                (const uint64_t*)(di + p.off_rand), (g1a*)(w + P), w + set_code, (uint32_t*)(w + n_bad), nullptr, 0u,
-                (uint32_t*)(w + mlist), (uint32_t*)(w + mlist) + n, nullptr, nullptr);
+  if constexpr (bits_mode) {
+    if (n)
+      launch_set_pk_bits(s, n, (const uint32_t*)(di + p.off_pks), committee_src(*c, sets[lo].slot), c->tab_aff.as<const g1a>(),
+                         c->tab_code.as<const uint8_t>(), c->tab_n, (const uint64_t*)(di + p.off_rand), (g1a*)(w + P), w + set_code,
+                         (uint32_t*)(w + n_bad), nullptr, nullptr, 1u);
+  } else {
+    launch_set_pk(s, n, p.K, (const uint32_t*)(di + p.off_pkoff), bytes_mode ? (const g1a*)(w + pk_aff) : c->tab_aff.as<const g1a>(),
+                  bytes_mode ? (const uint8_t*)(w + pk_code) : c->tab_code.as<const uint8_t>(), (const uint64_t*)(di + p.off_rand),
+                  (g1a*)(w + P), w + set_code, (uint32_t*)(w + n_bad), bytes_mode ? nullptr : (const uint32_t*)(di + p.off_pks),
+                  bytes_mode ? 0u : c->tab_n, (uint32_t*)(w + mlist), (uint32_t*)(w + mlist) + n, nullptr, nullptr);
+  }
   hipLaunchKernelGGL(k_sig_check, g, blk, 0, s, di + p.off_sigs, n, (g2a*)(w + sig_aff), w + sig_use, w + sig_code, (uint32_t*)(w + n_bad), 0u);
   hipLaunchKernelGGL(k_set_hash, g, blk, 0, s, di + p.off_msgs, (const uint32_t*)(di + p.off_msgoff), di + p.off_dst, 43u, n, (g2a*)(w + Q),
                      w + skip);
@@ -1734,7 +1827,8 @@ static int run_each(int d, const tbls_set* sets, size_t lo, size_t hi, uint8_t* 
 
 #define TB_EACH_CHUNK 65536u  // sets per device pass (bounds staging and workspace)
 
-extern "C" int tbls_verify_each(const tbls_set* sets, size_t n, int n_gpus, int* ok_per_set) {
+template <class SET>
+static int verify_each_impl(const SET* sets, size_t n, int n_gpus, int* ok_per_set) {
   const caller_device keep;
   if (ensure_init()) return TBLS_DEVICE_ERROR;
   if (n == 0) return TBLS_SUCCESS;
@@ -1765,15 +1859,20 @@ extern "C" int tbls_verify_each(const tbls_set* sets, size_t n, int n_gpus, int*
   return TBLS_SUCCESS;
 }
 
+extern "C" int tbls_verify_each(const tbls_set* sets, size_t n, int n_gpus, int* ok_per_set) {
+  return verify_each_impl(sets, n, n_gpus, ok_per_set);
+}
+
 // fastAggregateVerify of every set (config 2: sync-committee sets of 512 keys).
 // A randomized batch over the sets with keys settles the common all-valid
 // case with one final exponentiation: it accepts iff every set verifies (with
 // probability 1 - 2^-64 per forged set), and then every such set's verdict is
 // 1.  Otherwise the per-set pass (tbls_verify_each) gives the verdicts.
-extern "C" int tbls_fast_aggregate_verify_many(const tbls_set* sets, size_t n, int* ok_per_set) {
+template <class SET>
+static int fast_aggregate_verify_many_impl(const SET* sets, size_t n, int* ok_per_set) {
   if (ensure_init()) return TBLS_DEVICE_ERROR;
   if (n == 0) return TBLS_SUCCESS;
-  std::vector<tbls_set> keyed;
+  std::vector<SET> keyed;
   std::vector<size_t> pos;
   for (size_t i = 0; i < n; i++) {
     ok_per_set[i] = 0;  // empty key list -> false (BLS.java:193-195)
@@ -1793,7 +1892,103 @@ extern "C" int tbls_fast_aggregate_verify_many(const tbls_set* sets, size_t n, i
       return TBLS_SUCCESS;
     }
   }
-  return tbls_verify_each(sets, n, 1, ok_per_set);
+  return verify_each_impl(sets, n, 1, ok_per_set);
+}
+
+extern "C" int tbls_fast_aggregate_verify_many(const tbls_set* sets, size_t n, int* ok_per_set) {
+  return fast_aggregate_verify_many_impl(sets, n, ok_per_set);
+}
+
+// The same with keys by table index: the batch and the per-set pass read the
+// resident table (no upload, decompression or subgroup check of keys); the
+// table and every index are checked under the device lock (check_keys).
+extern "C" int tbls_fast_aggregate_verify_many_idx(const tbls_set_idx* sets, size_t n, int* ok_per_set) {
+  if (n && (!sets || !ok_per_set)) return TBLS_BAD_ARGUMENT;
+  for (size_t i = 0; i < n; i++)
+    if (sets[i].n_pks && !sets[i].key_idx) return TBLS_BAD_ARGUMENT;
+  return fast_aggregate_verify_many_impl(sets, n, ok_per_set);
+}
+
+// --------------------------------------------------------------------------
+// resident committees: the index list, the bad-member mask and the valid
+// members' sum on every device, beside its key table
+// --------------------------------------------------------------------------
+extern "C" int tbls_committee_load(uint32_t slot, const uint32_t* key_idx, uint32_t size) {
+  const caller_device keep;
+  if (ensure_init()) return TBLS_DEVICE_ERROR;
+  if (slot >= TBLS_COMMITTEE_SLOTS || !key_idx || size == 0 || size > TBLS_COMMITTEE_MAX) return TBLS_BAD_ARGUMENT;
+  std::vector<dev_ctx*> devs;
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    devs = g_ctx;
+  }
+  for (dev_ctx* c : devs) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->dev));
+    if (!c->tab_n) return TBLS_BAD_ARGUMENT;
+    for (uint32_t i = 0; i < size; i++)
+      if (key_idx[i] >= c->tab_n) return TBLS_BAD_ARGUMENT;
+    hipStream_t s = c->stream;
+    HIPCHK(hipStreamSynchronize(s));
+    c->cm_size[slot] = 0;
+    if (c->cmt.ensure((size_t)TBLS_COMMITTEE_SLOTS * TB_CM_STRIDE)) return TBLS_DEVICE_ERROR;
+    uint8_t* m = c->cmt.as<uint8_t>((size_t)slot * TB_CM_STRIDE);
+    HIPCHK(hipMemsetAsync(m, 0, TB_CM_STRIDE, s));
+    HIPCHK(hipMemcpyAsync(m, key_idx, (size_t)size * 4, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_committee_mask, dim3(1), dim3(TB_CM_WORDS), 0, s, (const uint32_t*)m, size, c->tab_code.as<const uint8_t>(),
+                       c->tab_n, (uint32_t*)(m + TB_CM_OFF_BAD), (uint32_t*)(m + TB_CM_OFF_VALID));
+    // the committee sum: one set whose participants are the valid members,
+    // on the direct side with r = 1; an exceptional addition is resolved by
+    // the kernel's one-lane body, so only a sum at infinity leaves a code
+    bits_src all = {(const uint32_t*)m, (const uint32_t*)(m + TB_CM_OFF_BAD), (const g1a*)(m + TB_CM_OFF_SUM), size, 0u, TB_CM_WORDS};
+    launch_set_pk_bits(s, 1, (const uint32_t*)(m + TB_CM_OFF_VALID), all, c->tab_aff.as<const g1a>(), c->tab_code.as<const uint8_t>(),
+                       c->tab_n, nullptr, (g1a*)(m + TB_CM_OFF_SUM), m + TB_CM_OFF_CODE, (uint32_t*)(m + TB_CM_OFF_CODE + 4), nullptr, nullptr,
+                       1u);
+    HIPCHK(hipGetLastError());
+    uint8_t code = 0xff;
+    HIPCHK(hipMemcpyAsync(&code, m + TB_CM_OFF_CODE, 1, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    c->cm_sum_ok[slot] = code == TB_SUCCESS ? 1u : 0u;
+    c->cm_size[slot] = size;
+  }
+  return TBLS_SUCCESS;
+}
+
+extern "C" uint32_t tbls_committee_size(uint32_t slot) {
+  if (slot >= TBLS_COMMITTEE_SLOTS || ensure_init()) return 0;
+  dev_ctx* c = ctx_for(0);
+  std::lock_guard<std::mutex> lk(c->mu);
+  return c->cm_size[slot];
+}
+
+// fastAggregateVerify of sets given as participation bitvectors over the
+// committee in `slot` (BlockProcessorAltair.java:234-267): the same two steps
+// over the sets with a participant -- the randomized batch, then the per-set
+// pass -- with the keys' stage on k_set_pk_bits_coop.
+extern "C" int tbls_fast_aggregate_verify_many_bits(uint32_t slot, const tbls_set_bits* sets, size_t n, int* ok_per_set) {
+  if (n && (!sets || !ok_per_set)) return TBLS_BAD_ARGUMENT;
+  const uint32_t size = tbls_committee_size(slot);
+  if (!size) return ensure_init() ? TBLS_DEVICE_ERROR : TBLS_BAD_ARGUMENT;
+  const uint32_t nb = (size + 7u) / 8u;
+  std::vector<set_bits_i> part;
+  std::vector<size_t> pos;
+  for (size_t i = 0; i < n; i++) {
+    if (!sets[i].bits || !sets[i].sig) return TBLS_BAD_ARGUMENT;
+    if ((size & 7u) && (sets[i].bits[nb - 1] >> (size & 7u))) return TBLS_BAD_ARGUMENT;  // a bit past the committee
+    uint8_t any = 0;
+    for (uint32_t k = 0; k < nb; k++) any |= sets[i].bits[k];
+    ok_per_set[i] = 0;  // no participant: an empty key list (BLS.java:193-195)
+    if (any) {
+      part.push_back({sets[i].bits, bits_stride_w(size), sets[i].msg, sets[i].msg_len, sets[i].sig, slot, size});
+      pos.push_back(i);
+    }
+  }
+  if (part.empty()) return TBLS_SUCCESS;
+  std::vector<int> ok(part.size(), 0);
+  const int rc = fast_aggregate_verify_many_impl(part.data(), part.size(), ok.data());
+  if (rc != TBLS_SUCCESS) return rc;
+  for (size_t k = 0; k < part.size(); k++) ok_per_set[pos[k]] = ok[k];
+  return TBLS_SUCCESS;
 }
 
 extern "C" int tbls_aggregate_verify(const uint8_t* pks, const uint8_t* const* msgs, const uint32_t* msg_lens, size_t n, const uint8_t sig[96],

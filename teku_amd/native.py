@@ -26,6 +26,8 @@ DEVICE_ERROR = 8
 BAD_ARGUMENT = 9
 
 PARTIAL_BYTES = 580
+COMMITTEE_SLOTS = 4
+COMMITTEE_MAX = 2048
 
 
 class TblsSet(ctypes.Structure):
@@ -44,6 +46,17 @@ class TblsSetIdx(ctypes.Structure):
     _fields_ = [
         ("key_idx", ctypes.c_void_p),
         ("n_pks", ctypes.c_uint32),
+        ("msg", ctypes.c_void_p),
+        ("msg_len", ctypes.c_uint32),
+        ("sig", ctypes.c_void_p),
+    ]
+
+
+class TblsSetBits(ctypes.Structure):
+    """tbls_set_bits: a set given as a participation bitvector over a resident committee."""
+
+    _fields_ = [
+        ("bits", ctypes.c_void_p),
         ("msg", ctypes.c_void_p),
         ("msg_len", ctypes.c_uint32),
         ("sig", ctypes.c_void_p),
@@ -152,6 +165,13 @@ _SIGS = {
             ctypes.POINTER(ctypes.c_int),
             ctypes.POINTER(TblsTiming),
         ],
+    ),
+    "tbls_fast_aggregate_verify_many_idx": (ctypes.c_int, [ctypes.POINTER(TblsSetIdx), ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]),
+    "tbls_committee_load": (ctypes.c_int, [ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32]),
+    "tbls_committee_size": (ctypes.c_uint32, [ctypes.c_uint32]),
+    "tbls_fast_aggregate_verify_many_bits": (
+        ctypes.c_int,
+        [ctypes.c_uint32, ctypes.POINTER(TblsSetBits), ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)],
     ),
     "tbls_dev_batch_partial_idx": (
         ctypes.c_int,
