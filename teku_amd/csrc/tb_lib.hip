@@ -24,10 +24,14 @@
 #include "tb_kdecl_mid.h"
 #include "tb_hrow.h"
 #include "tb_host.h"
+#include "tb_plan.h"  // every host-side decision: kernel choice, pair split, product levels, workspace layout, placement
 
 static_assert(TB_PARTIAL_BYTES == TBLS_PARTIAL_BYTES, "partial record size");
+static_assert(tb::plan::LINE_BYTES_PER_PAIR == TB_LINE_BYTES_PER_PAIR, "tb_plan.h: line bytes per pair");
+static_assert(tb::plan::HROW_SET_BYTES == sizeof(tb::hrow_set), "tb_plan.h: row-hash workspace per set");
 
 using tb::caller_device;
+using namespace tb::plan;
 
 namespace {
 
@@ -117,108 +121,10 @@ std::mutex g_mu;
 std::vector<dev_ctx*> g_ctx;
 bool g_inited = false;
 
-size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+uint32_t shard_min() { return plan_env::get().shard_min; }
+uint32_t shard_knee() { return plan_env::get().shard_knee; }
 
-// ---------------------------------------------------------------------------
-// Placement of a batch on the devices.  The reference runs
-// numThreads service workers side by side, each with its own batch
-// (AggregatingSignatureVerificationService.java:121-132, 202-205), so a
-// device should hold one caller's batch, not a slice of every caller's:
-//  * a batch is sharded only over devices that are IDLE at placement time
-//    (no batch in flight), and only into shards of at least shard_min sets:
-//    G = min(idle devices, n_gpus cap, floor(n / shard_min)) >= 1.
-//    shard_min = 32,768 sets, where one MI355X's partial stops being a
-//    latency chain (profiles/r04_stage_sweep_final.json, device partial:
-//    16,384 sets 8.6 ms = 1.9 M sets/s, 32,768 sets 12.5 ms = 2.6 M/s, 65,536
-//    21.8 ms = 3.0 M/s, 131,072 37.4 ms = 3.5 M/s); below it a second device
-//    buys a lone batch a few ms of latency and costs every concurrent caller a
-//    whole device.  So a lone 131,072-set batch runs as 4 shards of 32,768,
-//    1,048,576 sets over all 8 devices, and 8 workers with 16,384-set batches
-//    (config 4) take 8 different devices, one each;
-//  * with no idle device the batch goes whole to the least-loaded one;
-//  * among equals, ties are broken round-robin from a counter; the chosen
-//    devices are taken in ascending order (lock order; the lowest is the
-//    gather root);
-//  * shards are contiguous and balanced by key count, as teku_amd/dist.py
-//    shard_bounds.
-// (Round 4 sharded any batch of 2 x 2,048 sets over the least-loaded devices
-// whatever their load: a 16,384-set batch took all 8 devices and concurrent
-// workers serialized on them -- about 2.5 M sigs/s for the node where one
-// batch per device gives about 13.9 M)
-//  * on an IDLE NODE (no batch in flight on any device) a lone batch may
-//    shard further, down to the latency knee of TB_SHARD_KNEE = 4,096 sets
-//    per device (the same sweep: the device partial is 5.5 ms at 1,024 sets,
-//    5.8 at 4,096, 6.5 at 8,192, 8.6 at 16,384), so a lone config-4 batch of
-//    16,384 sets runs as 4 shards of 4,096: modelled latency 8.6 + 0.8 (final)
-//    -> 5.8 + 0.8 ms plus the record gather.  Under load the rule above
-//    holds: one device per batch.  A service that knows more batches are
-//    waiting passes n_gpus = 1 (teku_amd/service.py, and the Java mirror
-//    HipAggregatingSignatureVerificationService), so the first of several
-//    queued batches does not take the whole idle node.
-// TBLS_SHARD_MIN = "min[,knee]" overrides shard_min and the knee (min 0:
-// every allowed idle device).  tbls_place_plan exposes the same function for
-// CPU tests.
-// ---------------------------------------------------------------------------
-#define TB_SHARD_MIN 32768u
-#define TB_SHARD_KNEE 4096u
-struct shard_env_t {
-  uint32_t smin, knee;
-};
-static const shard_env_t& shard_env() {
-  static const shard_env_t v = [] {
-    shard_env_t e{TB_SHARD_MIN, TB_SHARD_KNEE};
-    const char* s = getenv("TBLS_SHARD_MIN");
-    if (s) {
-      unsigned a = 0, b = 0;
-      const int k = sscanf(s, "%u,%u", &a, &b);
-      if (k >= 1) e.smin = a;
-      e.knee = k == 2 ? b : std::min(e.smin, (uint32_t)TB_SHARD_KNEE);
-    }
-    return e;
-  }();
-  return v;
-}
-uint32_t shard_min() { return shard_env().smin; }
-uint32_t shard_knee() { return shard_env().knee; }
-
-// n sets (keys(i) keys each) over D devices with loads load[0..D): returns G
-// and fills dev[0..G) (ascending) and cut[0..G] (cut[0] = 0, cut[G] = n).
-// knee (0: none): the shard size floor when every device is idle.
-template <class KEYS>
-int place_plan(size_t n, const KEYS& keys, int D, int n_gpus, const int* load, uint32_t rr, uint32_t smin, uint32_t knee, int* dev,
-               size_t* cut) {
-  if (D < 1) return 0;
-  const int Gmax = (n_gpus > 0 && n_gpus < D) ? n_gpus : D;
-  std::vector<int> order(D);
-  for (int d = 0; d < D; d++) order[d] = d;
-  // least loaded first, ties round-robin from rr
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-    const int la = load ? load[a] : 0, lb = load ? load[b] : 0;
-    if (la != lb) return la < lb;
-    return (uint32_t)(a - (int)(rr % (uint32_t)D) + D) % (uint32_t)D < (uint32_t)(b - (int)(rr % (uint32_t)D) + D) % (uint32_t)D;
-  });
-  int idle = 0;
-  while (idle < D && (!load || load[order[idle]] == 0)) idle++;
-  if (idle == D && knee && smin && knee < smin) smin = knee;  // idle node: shard down to the latency knee
-  const size_t g = smin ? n / smin : (size_t)Gmax;
-  int G = (int)std::min<size_t>(std::max<size_t>(g, 1), (size_t)std::min(Gmax, std::max(idle, 1)));
-  if ((size_t)G > n) G = n ? (int)n : 1;
-  std::sort(order.begin(), order.begin() + G);
-  for (int k = 0; k < G; k++) dev[k] = order[k];
-  uint64_t totalK = 0;
-  for (size_t i = 0; i < n; i++) totalK += keys(i) + 1;
-  for (int k = 0; k <= G; k++) cut[k] = n;
-  cut[0] = 0;
-  uint64_t acc = 0;
-  int k = 1;
-  for (size_t i = 0; i < n && k < G; i++) {
-    acc += keys(i) + 1;
-    while (k < G && acc * G >= totalK * (uint64_t)k) cut[k++] = i + 1;
-  }
-  return G;
-}
-
-// The live placement: plan under g_place_mu and count the batch on its
+// The live placement (tb_plan.h place_plan): plan under g_place_mu and count the batch on its
 // devices until the guard ends.
 std::mutex g_place_mu;
 uint32_t g_place_rr = 0;
@@ -250,234 +156,6 @@ void place_one(placed& pl) {
   place_batch(pl, 1, [](size_t) { return 1u; }, 0, 1, 0);
 }
 
-// --------------------------------------------------------------------------
-// workspace layout for one device pipeline over n sets / K keys
-// --------------------------------------------------------------------------
-// Fp12 product levels: each wave multiplies TB_PROD_CHUNK values (k_fp12_prod_wave)
-#define TB_PROD_CHUNK 16u
-// From this many sets on, the signature side of the batch equation is a
-// bucket sum by randomizer byte with 2040 bucket pairs (k_msm_*, k_sigs.hip);
-// below it, one signature pair (-[r_i] g1, sig_i) per set.
-// (Round 4: 32,768 -> 20,480 sets.  24,576-set batches gain -- device partial
-// 13.65 -> 11.63 ms, host-API p50 15.7 -> 12.8 -- but at 12,288 and 16,384
-// sets the host-API p50 turns bimodal, 9.6 -> 12.4 ms (best runs 9.1; most
-// likely the bucket-sum kernels still resident when the one-round quad line
-// kernel launches push some of its waves into a second round); profiles/r04_stage_msm_min.json,
-// r04_cfg4_msm_ab.json.)
-#define TB_MSM_MIN 20480u
-// TBLS_MSM_MIN overrides (tuning)
-static uint32_t msm_min() {
-  static const uint32_t v = getenv("TBLS_MSM_MIN") ? (uint32_t)atoi(getenv("TBLS_MSM_MIN")) : TB_MSM_MIN;
-  return v;
-}
-#define TB_HASH_WAVE_MAX 512u  // k_set_hash_wave (one workgroup per set) up to this many sets: at 1024 its waves fill every SIMD and the key / signature stages can no longer run beside it (measured 9.8 vs 8.8 ms partial)
-#define TB_MSM_BUCKETS 2048u  // 8 windows x 256 digits (digit 0 unused)
-#define TB_MSM_NSUM 2040u     // 8 x 255 bucket sums
-#define TB_MSM_TREE_WG (TB_MSM_NSUM / 2u)  // k_msm_bucket_tree workgroups: two buckets of 32 lanes each (k_sigs.hip)
-#define TB_MSM_XPAIRS 64u     // 8 windows x 8 digit bits: the signature side's pairs
-// Split Miller loop (k_miller_lines + k_miller_acc*, k_lines.hip): pairs per
-// line-buffer chunk (19,584 B of lines per pair: 5.1 GB per chunk), and the
-// pair count from which two pairs share an accumulator (the GPU is full at one
-// accumulator wave per SIMD: 1024 waves x 64 lanes x 2 pairs).
-#define TB_LINE_CHUNK 262144u
-#define TB_MILLER_PER2_MIN 131072u
-// up to this many pairs, one pair per 64-lane workgroup (k_miller_wave);
-// TBLS_MILLER_WAVE_MAX overrides (tuning).  (Round 6 measured the level
-// program on 16 coop rows, k_miller_coop: one pair's loop 1.00 ms against
-// the wave kernel's 0.84 at 128 sets, profiles/r06_latency_128_coop_vs_wave.json;
-// not kept.)
-static uint32_t miller_wave_max() {
-  static const uint32_t v = getenv("TBLS_MILLER_WAVE_MAX") ? (uint32_t)atoi(getenv("TBLS_MILLER_WAVE_MAX")) : 2048u;
-  return v;
-}
-
-// Pairs of a batch of n sets: [0, n) the sets' (r_i apk_i, H(m_i)), then the
-// signature side -- n pairs (-[r_i] g1, sig_i) below TB_MSM_MIN sets (ordinary
-// pairs of the Miller kernels), else TB_MSM_XPAIRS bit-sum pairs.  With the
-// split Miller loop the bit-sum pairs run one 64-lane wave each (k_miller_wave,
-// n_xwave of them) on the bucket-sum stream, into the Miller values after the
-// accumulators'.
-// Segmented accumulator (k_lines.hip k_miller_accs_lds): `per` pairs per thread,
-// the loop's 68 steps in `nseg` segments.  Chosen to minimize the modelled
-// accumulator time: per-thread latency (68 / nseg) (12 + 13 per) Fp2
-// products (one f^2, per sparse line products per step) times the wave rounds
-// (TB_ACC_FULL threads = one 64-lane wave per SIMD fill the GPU once), plus
-// the Horner tail of the segment products (k_fp12_seg_combine_coop: ~63 (1 -
-// 1/nseg) Fp12 squarings, about one Fp2-product latency each); ties go to
-// fewer segments (smaller product tree).  TBLS_ACC_PLAN="per,nseg" overrides
-// it (tuning; per and nseg powers of two up to TB_ACC_PER_MAX /
-// TB_ACC_NSEG_MAX; "0" selects the unsegmented k_miller_acc1/2).  Every per
-// divides TB_LINE_CHUNK, so the chunks of a large batch fill contiguous group
-// ranges (lo / per).  (Round 4: per up to 16 and nseg up to 16 -- 16 x 8 at
-// 131,072 pairs, 8 x 16 at config 4's 32,768 -- where round 3 stopped at 8 x 4;
-// profiles/r04_bench_accplans.json.)
-#define TB_ACC_FULL 65536u
-#define TB_ACC_PER_MAX 16  // 32 x 16 measured slower than 16 x 8 at 131,072 pairs (13.9 vs 13.3 ms Miller stage)
-#define TB_ACC_NSEG_MAX 16
-// TBLS_ACC_PLAN: -1 / -1 (unset), 0 / 0 ("0": unsegmented), or per / nseg
-static void acc_env(int& e_per, int& e_seg) {
-  e_per = e_seg = -1;
-  const char* v = getenv("TBLS_ACC_PLAN");
-  if (!v) return;
-  if (v[0] == '0' && v[1] == 0) {
-    e_per = e_seg = 0;
-    return;
-  }
-  int p = 0, g = 0;
-  if (sscanf(v, "%d,%d", &p, &g) == 2 && p >= 1 && p <= 32 && (p & (p - 1)) == 0 && g >= 1 && g <= TB_ACC_NSEG_MAX) {  // per <= 32: one mask bit per pair
-    e_per = p;
-    e_seg = g;
-  }
-}
-struct acc_env_t {
-  int per, seg;
-};
-static void acc_plan(uint32_t n_main, uint32_t& per, uint32_t& nseg) {
-  // read once, thread-safe (C++11 magic static): concurrent batch callers plan at once
-  static const acc_env_t env = [] {
-    acc_env_t e;
-    acc_env(e.per, e.seg);
-    return e;
-  }();
-  const int e_per = env.per, e_seg = env.seg;
-  if (e_seg == 0) {  // the unsegmented kernels
-    per = n_main >= TB_MILLER_PER2_MIN ? 2u : 1u;
-    nseg = 1;
-    return;
-  }
-  double best = 0;
-  per = 1;
-  nseg = 1;
-  for (uint32_t p = 1; p <= (uint32_t)std::max(TB_ACC_PER_MAX, e_per); p *= 2) {
-    if (e_per > 0 && (int)p != e_per) continue;
-    for (uint32_t sg = 1; sg <= (uint32_t)TB_ACC_NSEG_MAX; sg++) {
-      if (e_seg > 0 ? (int)sg != e_seg : (sg & (sg - 1)) != 0) continue;
-      const double threads = (double)sg * ((n_main + p - 1) / p);
-      const double rounds = std::max(1.0, std::ceil(threads / TB_ACC_FULL));
-      const double cost = rounds * (68.0 / sg) * (12.0 + 13.0 * p) + (sg > 1 ? 63.0 * (1.0 - 1.0 / sg) : 0.0);
-      if (best == 0 || cost < best * 0.999) {
-        best = cost;
-        per = p;
-        nseg = sg;
-      }
-    }
-  }
-}
-struct pair_plan {
-  uint32_t n, n_extra, n_pairs, n_main, n_xwave, per, nseg;
-  bool msm, wave, split;
-  // settle: the per-set layout a failed batch is settled on (settle_sets):
-  // one signature pair per set (no bucket sums), split line / accumulator
-  // kernels at every size
-  explicit pair_plan(uint32_t n_, bool settle = false) : n(n_) {
-    msm = !settle && n >= msm_min();
-    n_extra = msm ? TB_MSM_XPAIRS : n;
-    n_pairs = n + n_extra;
-    wave = !settle && n_pairs <= miller_wave_max();
-    split = !wave;
-    n_xwave = split && msm ? n_extra : 0u;  // bit-sum pairs on their own waves
-    n_main = n_pairs - n_xwave;             // pairs owned by accumulator threads
-    nseg = 1;
-    per = 1;
-    if (split) acc_plan(std::min(n_main, TB_LINE_CHUNK), per, nseg);  // the chunks launch one after another: plan one chunk's fill
-  }
-  bool seg() const { return split && (nseg > 1 || per > 2); }  // k_miller_accs_lds
-  uint32_t n_groups() const { return (n_main + per - 1) / per; }
-  uint32_t n_f_main() const { return nseg * n_groups(); }
-  uint32_t n_f() const { return n_f_main() + n_xwave; }  // Miller values: accumulators (segment-major), then the wave pairs'
-  uint32_t line_pairs() const { return split ? std::min(n_main, TB_LINE_CHUNK) : 0u; }
-};
-
-// hash_to_G2 kernel by batch size above the workgroup-per-set kernels' range
-// (TB_HASH_WAVE_MAX): one 16-lane coop row per set (k_hrow.hip) up to row_max
-// sets, one DPP quad per set (k_hquad.hip k_set_hash_quad) up to quad_max,
-// one lane pair per set (k_set_hash_duo: an SSWU map per lane, the cofactor
-// clearing dealt over the pair) up to duo_max, then the one-lane
-// k_set_hash_w2.  A lane group fills the GPU at 65,536 lanes: quads at 16,384
-// sets leave no SIMD to the key and signature stages beside the hash
-// (profiles/r04_stage16k_quad_vs_pair.json), so quads stop at 8,192.  The
-// Miller lines use the same groups while they fit one wave per SIMD: quads
-// up to 16,384 pairs, pairs up to 32,768 (k_miller_lines_quad / _duo),
-// unless quad_max / duo_max is 0.  TBLS_HASH_PLAN = "row_max,quad_max,duo_max"
-// overrides the defaults (A/B; 0 disables a kernel).  (Round 3's pair kernel,
-// the SSWU maps on two lanes and the clearing on one, was removed once the
-// duo kernel replaced it: 16,384-set hash stage 5.10 -> 3.65 ms.)
-#define TB_HASH_ROW_MAX 1024u  // above, the quads win (4,096 sets: partial 6.98 -> 5.81 ms, profiles/r04_stage_row_vs_quad.json)
-#define TB_HASH_QUAD_MAX 8192u
-#define TB_HASH_DUO_MAX 32768u
-#define TB_GROUP_LANES 65536u  // one wave per SIMD
-struct hash_plan_t {
-  uint32_t row_max, quad_max, duo_max;
-};
-static const hash_plan_t& hash_plan() {
-  static const hash_plan_t v = [] {
-    hash_plan_t h{TB_HASH_ROW_MAX, TB_HASH_QUAD_MAX, TB_HASH_DUO_MAX};
-    const char* e = getenv("TBLS_HASH_PLAN");
-    unsigned r, q, d;
-    if (e && sscanf(e, "%u,%u,%u", &r, &q, &d) == 3) h = {r, q, d};
-    return h;
-  }();
-  return v;
-}
-static bool hash_row(uint32_t n) { return n > TB_HASH_WAVE_MAX && n <= hash_plan().row_max; }
-static bool hash_quad(uint32_t n) { return n > TB_HASH_WAVE_MAX && !hash_row(n) && n <= hash_plan().quad_max; }
-static bool hash_duo(uint32_t n) { return n > TB_HASH_WAVE_MAX && !hash_row(n) && !hash_quad(n) && n <= hash_plan().duo_max; }
-// lanes per pair of the Miller line kernel: 4, 2 or 1
-static int line_group(uint32_t n_main) {
-  if (hash_plan().quad_max && 4ull * n_main <= TB_GROUP_LANES) return 4;
-  if (hash_plan().duo_max && 2ull * n_main <= TB_GROUP_LANES) return 2;
-  return 1;
-}
-
-// Values per wave of the unsegmented product levels (k_fp12_prod_wave): a
-// wave multiplies its chunk one value after another, so small batches (the
-// latency path) take 4 (256 pairs: 4 levels of 3 products, against 2 levels
-// of 15 with 16); larger unsegmented batches keep TB_PROD_CHUNK.
-#ifndef TB_PROD_SMALL_MAX
-#define TB_PROD_SMALL_MAX 4096u
-#endif
-static uint32_t prod_chunk(const pair_plan& pp) { return !pp.seg() && pp.n_f() <= TB_PROD_SMALL_MAX ? 4u : TB_PROD_CHUNK; }
-
-struct ws_layout {
-  size_t pk_aff, pk_code, P, Q, skip, set_code, sig_code, f, fpart, fpart2, segv, n_bad, result;
-  size_t sig_aff, sig_use, msm_cnt, msm_off, msm_cur, msm_idx, msm_sum, mlist, mcnt, lines, hrow, total;
-  uint32_t nb_f;
-  ws_layout() : total(0) {}
-  ws_layout(const pair_plan& pp, uint32_t K) {
-    const uint32_t n = pp.n, np = pp.n_pairs, nf = pp.n_f();
-    const bool msm = pp.msm;
-    // first product level; segmented: nseg rows of the last segment's width
-    const uint32_t pc = prod_chunk(pp);
-    nb_f = (nf + pc - 1) / pc + pp.nseg * ((pp.n_groups() + pp.n_xwave + TB_PROD_CHUNK - 1) / TB_PROD_CHUNK);
-    size_t o = 0;
-    pk_aff = o;   o = align_up(o + (size_t)K * sizeof(g1a));
-    pk_code = o;  o = align_up(o + K);
-    P = o;        o = align_up(o + (size_t)np * sizeof(g1a));
-    Q = o;        o = align_up(o + (size_t)np * sizeof(g2a));
-    skip = o;     o = align_up(o + np);
-    set_code = o; o = align_up(o + np);  // extra pairs: zero codes
-    sig_code = o; o = align_up(o + np);
-    const size_t nm = msm ? n : 0;
-    sig_aff = o;  o = align_up(o + nm * sizeof(g2a));
-    sig_use = o;  o = align_up(o + nm);
-    msm_cnt = o;  o = align_up(o + (msm ? TB_MSM_BUCKETS * 4 : 0));
-    msm_off = o;  o = align_up(o + (msm ? (TB_MSM_BUCKETS + 1) * 4 : 0));
-    msm_cur = o;  o = align_up(o + (msm ? TB_MSM_BUCKETS * 4 : 0));
-    msm_idx = o;  o = align_up(o + nm * 8 * 4);
-    msm_sum = o;  o = align_up(o + (msm ? (size_t)TB_MSM_BUCKETS * sizeof(g2j) : 0));
-    mlist = o;    o = align_up(o + (size_t)n * 4);
-    mcnt = o;     o = align_up(o + 4);
-    hrow = o;     o = align_up(o + (hash_row(n) ? (size_t)n * sizeof(hrow_set) : 0));
-    lines = o;    o = align_up(o + (size_t)pp.line_pairs() * TB_LINE_BYTES_PER_PAIR);
-    f = o;        o = align_up(o + (size_t)(nf ? nf : 1) * sizeof(fp12));
-    fpart = o;    o = align_up(o + (size_t)nb_f * sizeof(fp12));
-    fpart2 = o;   o = align_up(o + (size_t)((nb_f + pc - 1) / pc + pp.nseg) * sizeof(fp12));
-    segv = o;     o = align_up(o + (size_t)pp.nseg * sizeof(fp12));
-    n_bad = o;    o = align_up(o + 4);
-    result = o;   o = align_up(o + 4);
-    total = o;
-  }
-};
 
 // Launch the partial pipeline for one device.  All pointers in `b` are
 // device pointers.  Writes the 580-byte partial record at `partial_out`.
@@ -494,56 +172,69 @@ struct ws_layout {
 // accumulator, acc_lds).  `serial`
 // (the stage-profile API) runs everything on the caller's stream, for
 // exclusive per-stage timings.
+struct bits_src;
+struct partial_opts {
+  const uint8_t* dst;  // hash_to_G2 domain separation tag, device memory
+  uint32_t dlen;
+  hipEvent_t* ev = nullptr;
+  bool serial = false;
+  const uint32_t* key_idx = nullptr;  // keys = indices into the resident table: no decompression
+  bool settle = false;                // the settle layout: per-set stages and the line kernel only (pair_plan)
+  const bits_src* cm = nullptr;       // the sets are bit rows over a resident committee (key_idx: the rows)
+};
 
-// The large-batch one-lane kernels (hash, signature check, [r] apk) as their
-// two-waves-per-SIMD twins (k_w2_*.hip) from TB_W2_MIN sets, where each
-// stage fills the GPU alone (throughput); TBLS_W2=0 selects the one-wave
-// kernels (A/B).  Below it the stages run side by side and each is a
-// latency chain: the one-wave kernels spill less, and a wave that holds the
-// whole register file keeps its SIMD to itself instead of sharing it with
-// another stage's two-wave waves (profiles/r04_stage16k_*).  (The Miller
-// line and accumulator kernels measured slower at two waves -- 17.5 and 24.3
-// vs 14.5 ms Miller stage at 131,072 sets, profiles/r04_bench_w2_masks.json
-// -- and stay at one.)
-#define TB_W2_MIN 32768u
-static bool w2(uint32_t n) {
-  static const bool v = !(getenv("TBLS_W2") && getenv("TBLS_W2")[0] == '0');
-  return v && n >= TB_W2_MIN;
-}
-// Small batches (<= TB_HASH_WAVE_MAX sets) run the key, signature and hash
-// stages, and multi-key aggregation, on the lane-cooperative kernels
-// (k_kcoop.hip, k_hwave.hip k_set_hash_coop); TBLS_COOP=0 selects the
-// one-thread / one-wave kernels they replaced (A/B, fall-back).
-static bool coop() {
-  static const bool v = !(getenv("TBLS_COOP") && getenv("TBLS_COOP")[0] == '0');
-  return v;
-}
+// The regions of a ws_layout as typed pointers into the workspace at w.
+struct ws_ptrs {
+  g1a *pk_aff, *P;
+  g2a *Q, *sig_aff;
+  uint8_t *pk_code, *skip, *set_code, *sig_code, *sig_use;
+  uint32_t *msm_cnt, *msm_off, *msm_cur, *msm_idx, *mlist, *mcnt, *n_bad;
+  g2j* msm_sum;
+  hrow_set* hrow;
+  uint4* lines;
+  fp12 *f, *fpart, *fpart2, *segv;
+  ws_ptrs(const ws_layout& L, uint8_t* w)
+      : pk_aff((g1a*)(w + L.pk_aff)), P((g1a*)(w + L.P)), Q((g2a*)(w + L.Q)), sig_aff((g2a*)(w + L.sig_aff)), pk_code(w + L.pk_code),
+        skip(w + L.skip), set_code(w + L.set_code), sig_code(w + L.sig_code), sig_use(w + L.sig_use), msm_cnt((uint32_t*)(w + L.msm_cnt)),
+        msm_off((uint32_t*)(w + L.msm_off)), msm_cur((uint32_t*)(w + L.msm_cur)), msm_idx((uint32_t*)(w + L.msm_idx)),
+        mlist((uint32_t*)(w + L.mlist)), mcnt((uint32_t*)(w + L.mcnt)), n_bad((uint32_t*)(w + L.n_bad)), msm_sum((g2j*)(w + L.msm_sum)),
+        hrow((hrow_set*)(w + L.hrow)), lines((uint4*)(w + L.lines)), f((fp12*)(w + L.f)), fpart((fp12*)(w + L.fpart)),
+        fpart2((fp12*)(w + L.fpart2)), segv((fp12*)(w + L.segv)) {}
+};
+
+// The affine keys a stage reads, with their validity codes: the call's own
+// decompressed keys (idx == nullptr, tab_n 0), or the resident table through
+// the indices idx (for a committee's sets: their bit rows).
+struct key_src {
+  const g1a* aff;
+  const uint8_t* code;
+  const uint32_t* idx;
+  uint32_t tab_n;
+};
+inline key_src own_keys(const g1a* aff, const uint8_t* code) { return {aff, code, nullptr, 0u}; }
+inline key_src table_keys(const dev_ctx& c, const uint32_t* idx) { return {c.tab_aff.as<const g1a>(), c.tab_code.as<const uint8_t>(), idx, c.tab_n}; }
 
 // Per-set aggregate key and P_i = [r_i] apk_i on stream s.  Single-key sets:
-// one thread per set (k_set_pk).  When some set has several keys (n_entries >
-// n: configs 2/3), those sets go to the wave-level aggregation k_set_pk_wave
+// one thread per set (k_set_pk, or its two-wave twin with w2: tb_plan.h
+// use_w2).  When some set has several keys (multi: tb_plan.h multi_key),
+// those sets go to the wave-level aggregation
 // through a device-built work list (mlist / mcnt: n + 1 words of workspace).
 // P2 (nullable): signature-pair points -[r_i] g1 (comb: the device's table).
-void launch_set_pk(hipStream_t s, uint32_t n, uint32_t n_entries, const uint32_t* pk_off, const g1a* aff, const uint8_t* code,
-                   const uint64_t* rand, g1a* P, uint8_t* set_code, uint32_t* n_bad, const uint32_t* key_idx, uint32_t tab_n,
-                   uint32_t* mlist, uint32_t* mcnt, g1a* P2, const g1a* comb) {
+void launch_set_pk(hipStream_t s, uint32_t n, bool w2, uint32_t multi, const uint32_t* pk_off, const key_src& ks, const uint64_t* rand, g1a* P,
+                   uint8_t* set_code, uint32_t* n_bad, uint32_t* mlist, uint32_t* mcnt, g1a* P2, const g1a* comb) {
   if (!n) return;
   const dim3 blk(TB_BLOCK), g((n + TB_BLOCK - 1) / TB_BLOCK);
-  // multi-key sets: the lane-cooperative aggregation (32 rows per set,
-  // k_kcoop.hip, with the set's -[r] g1), or the one-wave-per-set kernel with
-  // TBLS_COOP=0
-  const uint32_t multi = n_entries > n ? (coop() ? 2u : 1u) : 0u;
-  hipLaunchKernelGGL(w2(n) ? k_set_pk_w2 : k_set_pk, g, blk, 0, s, pk_off, aff, code, rand, n, P, set_code, n_bad, key_idx, tab_n, multi, P2,
+  hipLaunchKernelGGL(w2 ? k_set_pk_w2 : k_set_pk, g, blk, 0, s, pk_off, ks.aff, ks.code, rand, n, P, set_code, n_bad, ks.idx, ks.tab_n, multi, P2,
                      comb);
   if (!multi) return;
   (void)hipMemsetAsync(mcnt, 0, 4, s);
   hipLaunchKernelGGL(k_multi_list, g, blk, 0, s, pk_off, n, mlist, mcnt);
   if (multi == 2)
-    hipLaunchKernelGGL(k_set_pk_agg_coop, dim3(std::min<uint32_t>(n, 4096u)), dim3(512), 0, s, pk_off, aff, code, rand,
-                       (const uint32_t*)mlist, (const uint32_t*)mcnt, P, set_code, n_bad, key_idx, tab_n, P2, comb, 0u);
+    hipLaunchKernelGGL(k_set_pk_agg_coop, dim3(std::min<uint32_t>(n, 4096u)), dim3(512), 0, s, pk_off, ks.aff, ks.code, rand,
+                       (const uint32_t*)mlist, (const uint32_t*)mcnt, P, set_code, n_bad, ks.idx, ks.tab_n, P2, comb, 0u);
   else
-    hipLaunchKernelGGL(k_set_pk_wave, dim3(std::min<uint32_t>(n, 4096u)), dim3(64), 0, s, pk_off, aff, code, rand,
-                       (const uint32_t*)mlist, (const uint32_t*)mcnt, P, set_code, n_bad, key_idx, tab_n);
+    hipLaunchKernelGGL(k_set_pk_wave, dim3(std::min<uint32_t>(n, 4096u)), dim3(64), 0, s, pk_off, ks.aff, ks.code, rand,
+                       (const uint32_t*)mlist, (const uint32_t*)mcnt, P, set_code, n_bad, ks.idx, ks.tab_n);
 }
 
 // A resident committee on one device (dev_ctx::cmt) and the bit rows' stride.
@@ -566,14 +257,13 @@ inline bits_src committee_src(const dev_ctx& c, uint32_t slot) {
 }
 
 // launch_set_pk for sets given as participation bit rows over a resident
-// committee (rows: n rows of cm.stride_w words): one kernel, every set on the
+// committee (ks.idx: n rows of cm.stride_w words): one kernel, every set on the
 // lane-cooperative rows (k_set_pk_bits_coop), keys from the table.  unit_r: r = 1.
-void launch_set_pk_bits(hipStream_t s, uint32_t n, const uint32_t* rows, const bits_src& cm, const g1a* aff, const uint8_t* code,
-                        uint32_t tab_n, const uint64_t* rand, g1a* P, uint8_t* set_code, uint32_t* n_bad, g1a* P2, const g1a* comb,
-                        uint32_t unit_r) {
+void launch_set_pk_bits(hipStream_t s, uint32_t n, const key_src& ks, const bits_src& cm, const uint64_t* rand, g1a* P, uint8_t* set_code,
+                        uint32_t* n_bad, g1a* P2, const g1a* comb, uint32_t unit_r) {
   if (!n) return;
-  hipLaunchKernelGGL(k_set_pk_bits_coop, dim3(std::min<uint32_t>(n, 4096u)), dim3(512), 0, s, rows, cm.stride_w, cm.members, cm.size, cm.bad,
-                     cm.sum, cm.sum_ok, aff, code, tab_n, rand, n, P, set_code, n_bad, P2, comb, unit_r);
+  hipLaunchKernelGGL(k_set_pk_bits_coop, dim3(std::min<uint32_t>(n, 4096u)), dim3(512), 0, s, ks.idx, cm.stride_w, cm.members, cm.size, cm.bad,
+                     cm.sum, cm.sum_ok, ks.aff, ks.code, ks.tab_n, rand, n, P, set_code, n_bad, P2, comb, unit_r);
 }
 
 // k_lines.hip: the segmented accumulator with f in LDS and two lines per
@@ -594,15 +284,6 @@ extern "C" __global__ void k_miller_accs_lds(const uint4* __restrict__ lines, co
                                              fp12* __restrict__ f_out, uint32_t seg_stride);
 extern "C" __global__ void k_msm_bucket_tree(const g2a* __restrict__ sig_aff, const uint8_t* __restrict__ use, const uint32_t* __restrict__ off,
                                              const uint32_t* __restrict__ idx, g2j* __restrict__ bucket);  // k_sigs.hip
-// Bucket-sum batches: when the hash starts.  0: at once (beside the key
-// decompression and the signature checks); 1: after the signature checks;
-// 2: after the whole bucket-sum chain.  Measured at 131,072 sets
-// (profiles/r05_bench_sig_first.json): keys as bytes 36.4-36.7 ms (0) /
-// 37.8-37.9 (1) / 38.5-38.9 (2); keys from the device table 3.61-3.65 /
-// 3.87-3.90 / 3.70-3.74 M sigs/s.  So 1 with the key table (no key
-// decompression beside the signature checks), else 0.  (The A/B switch
-// TBLS_SIG_FIRST and order 2 were removed in round 6.)
-static int sig_first(bool key_table) { return key_table ? 1 : 0; }
 extern "C" __global__ void k_set_hash_wave(const uint8_t* __restrict__ msgs, const uint32_t* __restrict__ msg_off,
                                            const uint8_t* __restrict__ dst, uint32_t dlen, uint32_t n, g2a* __restrict__ Q,
                                            uint8_t* __restrict__ skip);  // k_hwave.hip
@@ -615,22 +296,205 @@ extern "C" __global__ void k_keys_coop(const uint8_t* __restrict__ pks, const ui
                                        uint8_t* __restrict__ set_code, uint32_t* __restrict__ n_bad, const g1a* __restrict__ comb);
 extern "C" __global__ void k_sig_check_coop(const uint8_t* __restrict__ sigs, uint32_t n, g2a* __restrict__ sig_aff, uint8_t* __restrict__ sig_use,
                                             uint8_t* __restrict__ sig_code, uint32_t* __restrict__ n_bad);  // k_kcoop.hip
-int launch_partial(dev_ctx& c, const tbls_dev_batch& b, hipStream_t s, void* partial_out, ws_layout& L,
-                   const uint8_t* dst, uint32_t dlen, hipEvent_t* ev = nullptr, bool serial = false,
-                   const uint32_t* key_idx = nullptr, bool settle = false, const bits_src* cm = nullptr) {
-  // cm: the sets are bit rows over a resident committee (key_idx: the rows)
+
+// One launch_partial call: the batch, its plan, the workspace and the streams
+// of its chains.  Each chain queues on one stream, in order; launch_partial
+// forks and joins them.
+struct partial_run {
+  dev_ctx& c;
+  const tbls_dev_batch& b;
+  const partial_opts& o;
+  const batch_plan& bp;
+  const ws_ptrs& W;
+  const key_src& keys;
+  hipStream_t s, sa, sb, sh;  // the caller's, keys, signatures + bucket sums, hash
+  bool late_join;             // bp.late_join with the streams side by side
   const uint32_t n = b.n;
-  const bool use_tab = key_idx != nullptr;  // keys = indices into the resident table: no decompression
-  const uint32_t K = use_tab ? 0 : b.n_keys;
-  const pair_plan pp(n, settle);
-  L = ws_layout(pp, K);
+  const dim3 blk = dim3(TB_BLOCK), g = dim3((b.n + TB_BLOCK - 1) / TB_BLOCK);  // one thread per set
+  g1a* sig_P() const { return bp.pp.msm ? nullptr : W.P + n; }                 // -[r_i] g1 of the sets' signature pairs
+
+#define TB_EV(i, st) \
+  if (o.ev) HIPCHK(hipEventRecord(o.ev[i], st))
+
+  // --- stream b: signatures, then (large batches) the bucket sums -----------
+  int sig_chain() const {
+    const pair_plan& pp = bp.pp;
+    if (pp.msm) {  // bucket sort by randomizer byte (randomizers only)
+      HIPCHK(hipMemsetAsync(W.msm_cnt, 0, TB_MSM_BUCKETS * 4, sb));
+      hipLaunchKernelGGL(k_msm_hist, g, blk, 0, sb, b.rand, n, W.msm_cnt);
+      hipLaunchKernelGGL(k_msm_scan, dim3(1), dim3(256), 0, sb, (const uint32_t*)W.msm_cnt, W.msm_off, W.msm_cur);
+      hipLaunchKernelGGL(k_msm_scatter, g, blk, 0, sb, b.rand, n, W.msm_cur, W.msm_idx);
+    }
+    TB_EV(4, sb);
+    if (n) {
+      const auto check = bp.w2 ? k_sig_check_w2 : k_sig_check;
+      if (bp.sig == sig_kind::msm)
+        hipLaunchKernelGGL(check, g, blk, 0, sb, b.sigs, n, W.sig_aff, W.sig_use, W.sig_code, W.n_bad, 0u);
+      else if (bp.sig == sig_kind::coop)
+        hipLaunchKernelGGL(k_sig_check_coop, dim3((n + 3) / 4), dim3(64), 0, sb, b.sigs, n, W.Q + n, W.skip + n, W.sig_code, W.n_bad);
+      else
+        hipLaunchKernelGGL(check, g, blk, 0, sb, b.sigs, n, W.Q + n, W.skip + n, W.sig_code, W.n_bad, 1u);
+    }
+    TB_EV(5, sb);
+    if (late_join) HIPCHK(hipEventRecord(c.e_sig, sb));  // the signature codes are there (batch_plan::late_join)
+    TB_EV(8, sb);
+    if (pp.msm) {
+      hipLaunchKernelGGL(k_msm_bucket_tree, dim3(TB_MSM_TREE_WG), dim3(64), 0, sb, (const g2a*)W.sig_aff, (const uint8_t*)W.sig_use,
+                         (const uint32_t*)W.msm_off, (const uint32_t*)W.msm_idx, W.msm_sum);
+      hipLaunchKernelGGL(k_msm_bitsum_pairs, dim3(TB_MSM_XPAIRS), dim3(64), 0, sb, (const g2j*)W.msm_sum, c.comb.as<const g1a>(), W.P + n,
+                         W.Q + n, W.skip + n);
+      if (pp.n_xwave)  // their Miller loops, one wave each, on this stream: f[n_f_main ..)
+        hipLaunchKernelGGL(k_miller_wave, dim3(pp.n_xwave), dim3(64), 0, sb, (const g1a*)W.P + n, (const g2a*)W.Q + n, (const uint8_t*)W.skip + n,
+                           (const uint8_t*)W.set_code + n, (const uint8_t*)W.sig_code + n, pp.n_xwave, W.f + pp.n_f_main());
+    }
+    TB_EV(9, sb);
+    return TBLS_SUCCESS;
+  }
+
+  // --- stream a: public keys, [r] apk (+ -[r] g1 for the signature pairs) -----
+  int key_chain() const {
+    const g1a* comb = c.comb.as<const g1a>();
+    TB_EV(0, sa);
+    if (bp.key == key_kind::bits) {
+      TB_EV(1, sa);
+      TB_EV(2, sa);
+      launch_set_pk_bits(sa, n, keys, *o.cm, b.rand, W.P, W.set_code, W.n_bad, sig_P(), comb, 0u);
+    } else if (bp.key == key_kind::keys_coop) {  // one kernel; its time shows as stage 0
+      const bool tab = keys.idx != nullptr;
+      hipLaunchKernelGGL(k_keys_coop, dim3((n + 3) / 4), dim3(128), 0, sa, tab ? nullptr : b.pks, b.pk_off, tab ? keys.aff : nullptr,
+                         tab ? keys.code : nullptr, keys.idx, keys.tab_n, b.rand, n, W.P, sig_P(), W.set_code, W.n_bad, comb);
+      TB_EV(1, sa);
+      TB_EV(2, sa);
+    } else {
+      if (bp.n_keys)
+        hipLaunchKernelGGL(k_pk_decompress, dim3((bp.n_keys + TB_BLOCK - 1) / TB_BLOCK), blk, 0, sa, b.pks, bp.n_keys, W.pk_aff, W.pk_code);
+      TB_EV(1, sa);
+      TB_EV(2, sa);
+      launch_set_pk(sa, n, bp.w2, bp.multi, b.pk_off, keys, b.rand, W.P, W.set_code, W.n_bad, W.mlist, W.mcnt, sig_P(), comb);
+    }
+    TB_EV(3, sa);
+    return TBLS_SUCCESS;
+  }
+
+  // --- high-priority stream: hash_to_G2 per set -------------------------------
+  // The longest per-set stage (2 wave rounds at 131k sets): with queue
+  // priority its waves are dispatched first and the shorter key / signature
+  // stages fill the SIMDs around them, instead of its last waves running
+  // alone after the others finish.
+  int hash_chain() const {
+    g2a* Q = W.Q;
+    uint8_t* skip = W.skip;
+    TB_EV(6, sh);
+    switch (bp.hash) {
+      case hash_kind::none:
+        break;
+      case hash_kind::coop:
+        hipLaunchKernelGGL(k_set_hash_coop, dim3(n), dim3(256), 0, sh, b.msgs, b.msg_off, o.dst, o.dlen, n, Q, skip, (const uint64_t*)nullptr);
+        break;
+      case hash_kind::wave:
+        hipLaunchKernelGGL(k_set_hash_wave, dim3(n), dim3(128), 0, sh, b.msgs, b.msg_off, o.dst, o.dlen, n, Q, skip);
+        break;
+      case hash_kind::row: {
+        hrow_set* H = W.hrow;
+        hipLaunchKernelGGL(k_hrow_field, g, blk, 0, sh, b.msgs, b.msg_off, o.dst, o.dlen, n, H);
+        hipLaunchKernelGGL(k_hrow_sswu, dim3((2 * n + 3) / 4), dim3(64), 0, sh, n, H);
+        hipLaunchKernelGGL(k_hrow_iso, g, blk, 0, sh, n, H);
+        hipLaunchKernelGGL(k_hrow_cof, dim3((n + 3) / 4), dim3(64), 0, sh, n, (const hrow_set*)H, Q, skip, 0);
+        hipLaunchKernelGGL(k_hrow_fix, g, blk, 0, sh, n, (const hrow_set*)H, Q, skip);
+        break;
+      }
+      case hash_kind::quad:
+        hipLaunchKernelGGL(k_set_hash_quad, dim3((4 * n + TB_BLOCK - 1) / TB_BLOCK), blk, 0, sh, b.msgs, b.msg_off, o.dst, o.dlen, n, Q, skip);
+        break;
+      case hash_kind::duo:
+        hipLaunchKernelGGL(k_set_hash_duo, dim3((2 * n + TB_BLOCK - 1) / TB_BLOCK), blk, 0, sh, b.msgs, b.msg_off, o.dst, o.dlen, n, Q, skip);
+        break;
+      case hash_kind::w2:
+        // the chains' affine addends wait in the line buffer (19,584 B per pair,
+        // unused until the line kernel, which runs after this stream joins)
+        hipLaunchKernelGGL(k_set_hash_w2, g, blk, 0, sh, b.msgs, b.msg_off, o.dst, o.dlen, n, Q, skip, (g2a*)W.lines);
+        break;
+      case hash_kind::lane:
+        hipLaunchKernelGGL(k_set_hash, g, blk, 0, sh, b.msgs, b.msg_off, o.dst, o.dlen, n, Q, skip);
+        break;
+    }
+    if (bp.hash == hash_kind::quad || bp.hash == hash_kind::duo || bp.hash == hash_kind::w2)  // the exact formulas for the sets it flags (skip == 2)
+      hipLaunchKernelGGL(k_set_hash_fix, g, blk, 0, sh, b.msgs, b.msg_off, o.dst, o.dlen, n, Q, skip);
+    TB_EV(7, sh);
+    return TBLS_SUCCESS;
+  }
+
+  // --- Miller loops of all pairs (pairs of invalid sets contribute 1) ---------
+  int miller() const {
+    const pair_plan& pp = bp.pp;
+    const uint32_t np = pp.n_pairs;
+    const g1a* P = W.P;
+    const g2a* Q = W.Q;
+    const uint8_t *skip = W.skip, *ca = W.set_code, *cb = W.sig_code;
+    TB_EV(10, s);
+    if (!np) return TBLS_SUCCESS;
+    if (pp.wave) {
+      hipLaunchKernelGGL(k_miller_wave, dim3(np), dim3(64), 0, s, P, Q, skip, ca, cb, np, W.f);
+      return TBLS_SUCCESS;
+    }
+    // chunks of the main pairs: G2 lines (P and T in LDS), then the Fp12
+    // accumulator (segment-major values: segment j of group g at f[j * n_groups + g])
+    const uint4* lines = W.lines;
+    const auto line_kernel = bp.line_group == 4 ? k_miller_lines_quad : bp.line_group == 2 ? k_miller_lines_duo : k_miller_lines_w2;  // mid-size batches: a lane group per pair
+    for (uint32_t lo = 0; lo < pp.n_main; lo += TB_LINE_CHUNK) {
+      const uint32_t m = std::min(TB_LINE_CHUNK, pp.n_main - lo), mt = (m + pp.per - 1) / pp.per;
+      hipLaunchKernelGGL(line_kernel, dim3((bp.line_group * m + TB_BLOCK - 1) / TB_BLOCK), blk, 0, s, P + lo, Q + lo, skip + lo, ca + lo, cb + lo, m,
+                         W.lines);
+      if (o.settle) continue;  // settle_sets accumulates per set from these lines
+      if (late_join && lo == 0) HIPCHK(hipStreamWaitEvent(s, c.e_join[1], 0));  // the bucket-sum stream first (acc_lds)
+      if (pp.seg()) {
+        const uint32_t g_pad = (mt + TB_BLOCK - 1) / TB_BLOCK * TB_BLOCK;
+        hipLaunchKernelGGL(k_miller_accs_lds, dim3(pp.nseg * g_pad / TB_BLOCK), blk, 0, s, lines, skip + lo, ca + lo, cb + lo, m, pp.per, pp.nseg,
+                           g_pad, W.f + lo / pp.per, pp.n_groups());
+      } else {
+        hipLaunchKernelGGL(pp.per == 2 ? k_miller_acc2 : k_miller_acc1, dim3((mt + TB_BLOCK - 1) / TB_BLOCK), blk, 0, s, lines, skip + lo, ca + lo,
+                           cb + lo, m, W.f + lo / pp.per);
+      }
+    }
+    return TBLS_SUCCESS;
+  }
+
+  // --- the partial: the product of the Miller values, by the plan's levels ----
+  int product_tree(void* partial_out) const {
+    TB_EV(12, s);
+    if (bp.pp.n_f() == 0) {  // no pairs at all: the partial product is 1
+      HIPCHK(hipMemsetAsync(W.f, 0, sizeof(fp12), s));
+      hipLaunchKernelGGL(k_fp12_one, dim3(1), dim3(64), 0, s, W.f);
+    }
+    const fp12* src = W.f;
+    for (int i = 0; i < bp.n_levels; i++) {
+      const prod_level& l = bp.levels[i];
+      fp12* out = l.dst == prod_dst::partial ? (fp12*)partial_out : l.dst == prod_dst::segv ? W.segv : l.dst == prod_dst::fpart2 ? W.fpart2 : W.fpart;
+      if (l.seg)
+        hipLaunchKernelGGL(k_fp12_prod_wave_seg, dim3(l.n_out, bp.pp.nseg), dim3(64), 0, s, src, l.n_in, l.n_in_last, bp.pp.nseg, l.in_stride,
+                           l.chunk, out, l.out_stride);
+      else
+        hipLaunchKernelGGL(k_fp12_prod_wave, dim3(l.n_out), dim3(64), 0, s, src, l.n_in, l.chunk, out);
+      src = out;
+    }
+    if (bp.combine)  // the Horner combine of the segment products
+      hipLaunchKernelGGL(k_fp12_seg_combine_coop, dim3(1), dim3(TB_CFE_THREADS), 0, s, (const fp12*)W.segv, bp.pp.nseg, 0u, (fp12*)partial_out);
+    TB_EV(13, s);
+    return TBLS_SUCCESS;
+  }
+};
+
+int launch_partial(dev_ctx& c, const tbls_dev_batch& b, hipStream_t s, void* partial_out, ws_layout& L, const partial_opts& o) {
+  const batch_plan bp(b.n, b.n_keys, o.cm ? key_source::bits : o.key_idx ? key_source::table : key_source::bytes, o.settle);
+  L = ws_layout(bp);
   tb::stat_add(tb::TB_STAT_PARTIALS);
   HIPCHK(ws_acquire(c, s));
   if (L.total > c.ws.cap) {  // growing frees the old buffer: drain its users first
     HIPCHK(hipStreamSynchronize(s));
     if (c.ws.ensure(L.total)) return TBLS_DEVICE_ERROR;
   }
-  uint8_t* w = c.ws.as<uint8_t>();
+  const ws_ptrs W(L, c.ws.as<uint8_t>());
+  const key_src keys = o.key_idx ? table_keys(c, o.key_idx) : own_keys(W.pk_aff, W.pk_code);
   // `serial` (tbls_dev_batch_stage_profile): every stage on the caller's
   // stream, for exclusive per-stage timings.  Otherwise the three per-set
   // chains (keys, signatures + bucket sums, hash) run side by side on their
@@ -639,100 +503,20 @@ int launch_partial(dev_ctx& c, const tbls_dev_batch& b, hipStream_t s, void* par
   // then; with round 4's kernels side by side wins everywhere: 16,384-set
   // partial unchanged, 32,768 sets 14.16 -> 12.44 ms, 65,536 26.11 -> 22.23,
   // 131,072 37.73 -> 36.15, profiles/r04_stage_chain_ab.json.)
-  hipStream_t sa = serial ? s : c.aux[0], sb = serial ? s : c.aux[1], sh = serial ? s : c.aux[2];
-  hipStream_t ssig = sb;
-#define TB_EV(i, st) \
-  if (ev) HIPCHK(hipEventRecord(ev[i], st))
-  const dim3 blk(TB_BLOCK);
-  const dim3 g((n + TB_BLOCK - 1) / TB_BLOCK);
-  g1a* P = (g1a*)(w + L.P);
-  g2a* Q = (g2a*)(w + L.Q);
-  uint8_t* skip = w + L.skip;
-  HIPCHK(hipMemsetAsync(w + L.set_code, 0, 2 * align_up(pp.n_pairs), s));  // set_code and sig_code (adjacent)
-  HIPCHK(hipMemsetAsync(w + L.n_bad, 0, 4, s));
-  if (!serial) {
+  const bool late_join = bp.late_join && !o.serial;
+  const partial_run run{c, b, o, bp, W, keys, s, o.serial ? s : c.aux[0], o.serial ? s : c.aux[1], o.serial ? s : c.aux[2], late_join};
+  HIPCHK(hipMemsetAsync(W.set_code, 0, 2 * align_up(bp.pp.n_pairs), s));  // set_code and sig_code (adjacent)
+  HIPCHK(hipMemsetAsync(W.n_bad, 0, 4, s));
+  if (!o.serial) {
     HIPCHK(hipEventRecord(c.e_fork, s));
-    HIPCHK(hipStreamWaitEvent(sa, c.e_fork, 0));
-    HIPCHK(hipStreamWaitEvent(sb, c.e_fork, 0));
-    HIPCHK(hipStreamWaitEvent(sh, c.e_fork, 0));
+    HIPCHK(hipStreamWaitEvent(run.sa, c.e_fork, 0));
+    HIPCHK(hipStreamWaitEvent(run.sb, c.e_fork, 0));
+    HIPCHK(hipStreamWaitEvent(run.sh, c.e_fork, 0));
   }
-  // --- stream b: signatures, then (large batches) the bucket sums -----------
-  uint32_t* msm_cnt = (uint32_t*)(w + L.msm_cnt);
-  uint32_t* msm_off = (uint32_t*)(w + L.msm_off);
-  uint32_t* msm_idx = (uint32_t*)(w + L.msm_idx);
-  if (pp.msm) {  // bucket sort by randomizer byte (randomizers only)
-    uint32_t* cur = (uint32_t*)(w + L.msm_cur);
-    HIPCHK(hipMemsetAsync(msm_cnt, 0, TB_MSM_BUCKETS * 4, sb));
-    hipLaunchKernelGGL(k_msm_hist, g, blk, 0, sb, b.rand, n, msm_cnt);
-    hipLaunchKernelGGL(k_msm_scan, dim3(1), dim3(256), 0, sb, (const uint32_t*)msm_cnt, msm_off, cur);
-    hipLaunchKernelGGL(k_msm_scatter, g, blk, 0, sb, b.rand, n, cur, msm_idx);
-  }
-  TB_EV(4, ssig);
-  if (n) {
-    if (pp.msm)
-      hipLaunchKernelGGL(w2(n) ? k_sig_check_w2 : k_sig_check, g, blk, 0, ssig, b.sigs, n, (g2a*)(w + L.sig_aff), w + L.sig_use,
-                         w + L.sig_code, (uint32_t*)(w + L.n_bad), 0u);
-    else if (n <= TB_HASH_WAVE_MAX && coop())  // the same, 4 sets per wave, lane-cooperative
-      hipLaunchKernelGGL(k_sig_check_coop, dim3((n + 3) / 4), dim3(64), 0, ssig, b.sigs, n, (g2a*)(Q + n), skip + n, w + L.sig_code,
-                         (uint32_t*)(w + L.n_bad));
-    else  // the set's signature pair: Q[n + i] = sig_i, skip[n + i] = infinite / invalid
-      hipLaunchKernelGGL(w2(n) ? k_sig_check_w2 : k_sig_check, g, blk, 0, ssig, b.sigs, n, Q + n, skip + n, w + L.sig_code,
-                         (uint32_t*)(w + L.n_bad), 1u);
-  }
-  TB_EV(5, ssig);
-  // Large split batches: the main pairs' line kernel needs only the signature
-  // codes from this stream, not the bucket sums and the extra pairs' Miller
-  // loops (one 64-lane launch of ~2.5 ms): it waits on e_sig, and only the
-  // product tree waits on e_join[1].
-  const bool late_join = !serial && pp.msm && pp.split;
-  if (late_join) HIPCHK(hipEventRecord(c.e_sig, sb));
-  TB_EV(8, sb);
-  if (pp.msm) {
-    hipLaunchKernelGGL(k_msm_bucket_tree, dim3(TB_MSM_TREE_WG), dim3(64), 0, sb, (const g2a*)(w + L.sig_aff), (const uint8_t*)(w + L.sig_use),
-                       (const uint32_t*)msm_off, (const uint32_t*)msm_idx, (g2j*)(w + L.msm_sum));
-    hipLaunchKernelGGL(k_msm_bitsum_pairs, dim3(TB_MSM_XPAIRS), dim3(64), 0, sb, (const g2j*)(w + L.msm_sum), c.comb.as<const g1a>(),
-                       P + n, Q + n, skip + n);
-    if (pp.n_xwave)  // their Miller loops, one wave each, on this stream: f[n_f_main ..)
-      hipLaunchKernelGGL(k_miller_wave, dim3(pp.n_xwave), dim3(64), 0, sb, (const g1a*)P + n, (const g2a*)Q + n, (const uint8_t*)skip + n,
-                         (const uint8_t*)(w + L.set_code + n), (const uint8_t*)(w + L.sig_code + n), pp.n_xwave, (fp12*)(w + L.f) + pp.n_f_main());
-  }
-  TB_EV(9, sb);
-  HIPCHK(hipEventRecord(c.e_join[1], sb));
-  // --- stream a: public keys, [r] apk (+ -[r] g1 for the signature pairs) -----
-  TB_EV(0, sa);
-  if (cm) {
-    TB_EV(1, sa);
-    TB_EV(2, sa);
-    launch_set_pk_bits(sa, n, key_idx, *cm, c.tab_aff.as<const g1a>(), c.tab_code.as<const uint8_t>(), c.tab_n, b.rand, P, w + L.set_code,
-                       (uint32_t*)(w + L.n_bad), pp.msm ? nullptr : P + n, c.comb.as<const g1a>(), 0u);
-  } else if (b.n_keys == n && n && n <= TB_HASH_WAVE_MAX && coop()) {
-    // one kernel: decode + G1 check (wave 0) beside -[r] g1, then [r] pk (wave
-    // 1); its time shows as stage 0.  As many keys as sets: one key per set
-    // in every real batch (a set of several keys beside empty ones still
-    // verifies correctly, on one lane).
-    hipLaunchKernelGGL(k_keys_coop, dim3((n + 3) / 4), dim3(128), 0, sa, use_tab ? nullptr : b.pks, b.pk_off,
-                       use_tab ? c.tab_aff.as<const g1a>() : nullptr, use_tab ? c.tab_code.as<const uint8_t>() : nullptr, key_idx,
-                       use_tab ? c.tab_n : 0u, b.rand, n, P, pp.msm ? nullptr : P + n, w + L.set_code, (uint32_t*)(w + L.n_bad),
-                       c.comb.as<const g1a>());
-    TB_EV(1, sa);
-    TB_EV(2, sa);
-  } else {
-    if (K)
-      hipLaunchKernelGGL(k_pk_decompress, dim3((K + TB_BLOCK - 1) / TB_BLOCK), blk, 0, sa, b.pks, K, (g1a*)(w + L.pk_aff), w + L.pk_code);
-    TB_EV(1, sa);
-    TB_EV(2, sa);
-    launch_set_pk(sa, n, b.n_keys, b.pk_off, use_tab ? c.tab_aff.as<const g1a>() : (const g1a*)(w + L.pk_aff),
-                  use_tab ? c.tab_code.as<const uint8_t>() : (const uint8_t*)(w + L.pk_code), b.rand, P, w + L.set_code,
-                  (uint32_t*)(w + L.n_bad), key_idx, use_tab ? c.tab_n : 0u, (uint32_t*)(w + L.mlist), (uint32_t*)(w + L.mcnt),
-                  pp.msm ? nullptr : P + n, c.comb.as<const g1a>());
-  }
-  TB_EV(3, sa);
-  HIPCHK(hipEventRecord(c.e_join[0], sa));
-  // --- high-priority stream: hash_to_G2 per set -------------------------------
-  // The longest per-set stage (2 wave rounds at 131k sets): with queue
-  // priority its waves are dispatched first and the shorter key / signature
-  // stages fill the SIMDs around them, instead of its last waves running
-  // alone after the others finish.
+  if (const int rc = run.sig_chain()) return rc;
+  HIPCHK(hipEventRecord(c.e_join[1], run.sb));
+  if (const int rc = run.key_chain()) return rc;
+  HIPCHK(hipEventRecord(c.e_join[0], run.sa));
   // Bucket-sum batches with the key table: the hash waits for the signature
   // checks (sig_first).  Every large per-set kernel is one round of
   // register-full waves, so whichever starts first holds the whole chip until
@@ -742,134 +526,32 @@ int launch_partial(dev_ctx& c, const tbls_dev_batch& b, hipStream_t s, void* par
   // ~1.4 ms for them with the chip nearly idle (rocprof trace of the 131k
   // step, profiles/r05_kernel_trace_step.txt).  With key decompression in
   // the batch the hash-first order still measured faster.
-  const int sf = sig_first(use_tab);
-  if (late_join && sf) HIPCHK(hipStreamWaitEvent(sh, c.e_sig, 0));
-  TB_EV(6, sh);
-  if (n && n <= TB_HASH_WAVE_MAX && coop())  // one 256-thread workgroup per set: coop SSWU chains and cofactor program
-    hipLaunchKernelGGL(k_set_hash_coop, dim3(n), dim3(256), 0, sh, b.msgs, b.msg_off, dst, dlen, n, Q, skip, (const uint64_t*)nullptr);
-  else if (n && n <= TB_HASH_WAVE_MAX)  // one workgroup per set: the cofactor clearing lane-parallel
-    hipLaunchKernelGGL(k_set_hash_wave, dim3(n), dim3(128), 0, sh, b.msgs, b.msg_off, dst, dlen, n, Q, skip);
-  else if (hash_row(n)) {  // one coop row per set (k_hrow.hip): five launches
-    hrow_set* H = (hrow_set*)(w + L.hrow);
-    hipLaunchKernelGGL(k_hrow_field, g, blk, 0, sh, b.msgs, b.msg_off, dst, dlen, n, H);
-    hipLaunchKernelGGL(k_hrow_sswu, dim3((2 * n + 3) / 4), dim3(64), 0, sh, n, H);
-    hipLaunchKernelGGL(k_hrow_iso, g, blk, 0, sh, n, H);
-    hipLaunchKernelGGL(k_hrow_cof, dim3((n + 3) / 4), dim3(64), 0, sh, n, (const hrow_set*)H, Q, skip, 0);
-    hipLaunchKernelGGL(k_hrow_fix, g, blk, 0, sh, n, (const hrow_set*)H, Q, skip);
-  } else if (hash_quad(n)) {  // one quad per set, then the exact formulas for the sets it flags (skip == 2)
-    hipLaunchKernelGGL(k_set_hash_quad, dim3((4 * n + TB_BLOCK - 1) / TB_BLOCK), blk, 0, sh, b.msgs, b.msg_off, dst, dlen, n, Q, skip);
-    hipLaunchKernelGGL(k_set_hash_fix, g, blk, 0, sh, b.msgs, b.msg_off, dst, dlen, n, Q, skip);
-  } else if (hash_duo(n)) {  // one lane pair per set, then the exact formulas for the sets it flags
-    hipLaunchKernelGGL(k_set_hash_duo, dim3((2 * n + TB_BLOCK - 1) / TB_BLOCK), blk, 0, sh, b.msgs, b.msg_off, dst, dlen, n, Q, skip);
-    hipLaunchKernelGGL(k_set_hash_fix, g, blk, 0, sh, b.msgs, b.msg_off, dst, dlen, n, Q, skip);
-  } else if (n && w2(n)) {  // two waves per SIMD, then the exact formulas for the sets it flags (skip == 2)
-    // the chains' affine addends wait in the line buffer (19,584 B per pair,
-    // unused until the line kernel, which runs after this stream joins)
-    hipLaunchKernelGGL(k_set_hash_w2, g, blk, 0, sh, b.msgs, b.msg_off, dst, dlen, n, Q, skip, (g2a*)(w + L.lines));
-    hipLaunchKernelGGL(k_set_hash_fix, g, blk, 0, sh, b.msgs, b.msg_off, dst, dlen, n, Q, skip);
-  } else if (n)
-    hipLaunchKernelGGL(k_set_hash, g, blk, 0, sh, b.msgs, b.msg_off, dst, dlen, n, Q, skip);
-  TB_EV(7, sh);
-  if (!serial) {
-    HIPCHK(hipEventRecord(c.e_join[2], sh));
+  if (late_join && bp.sig_first) HIPCHK(hipStreamWaitEvent(run.sh, c.e_sig, 0));
+  if (const int rc = run.hash_chain()) return rc;
+  if (!o.serial) {
+    HIPCHK(hipEventRecord(c.e_join[2], run.sh));
     HIPCHK(hipStreamWaitEvent(s, c.e_join[2], 0));
   }
   HIPCHK(hipStreamWaitEvent(s, c.e_join[0], 0));
   if (!late_join)
     HIPCHK(hipStreamWaitEvent(s, c.e_join[1], 0));
   else
-    HIPCHK(hipStreamWaitEvent(s, c.e_sig, 0));  // the set pairs' lines read the signature codes
-  // --- Miller loops of all pairs (pairs of invalid sets contribute 1) ---------
-  const uint32_t np = pp.n_pairs, nf = pp.n_f();
-  TB_EV(10, s);
-  if (np) {
-    const uint8_t* ca = w + L.set_code;
-    const uint8_t* cb = w + L.sig_code;
-    fp12* f = (fp12*)(w + L.f);
-    if (pp.wave) {
-      hipLaunchKernelGGL(k_miller_wave, dim3(np), dim3(64), 0, s, (const g1a*)P, (const g2a*)Q, (const uint8_t*)skip, ca, cb, np, f);
-    } else {
-      // chunks of the main pairs: G2 lines (P and T in LDS), then the Fp12
-      // accumulator (segment-major values: segment j of group g at f[j * n_groups + g])
-      uint4* lines = (uint4*)(w + L.lines);
-      for (uint32_t lo = 0; lo < pp.n_main; lo += TB_LINE_CHUNK) {
-        const uint32_t m = std::min(TB_LINE_CHUNK, pp.n_main - lo), mt = (m + pp.per - 1) / pp.per;
-        const int lg = line_group(pp.n_main);  // mid-size batches: a lane group per pair
-        if (lg > 1)
-          hipLaunchKernelGGL(lg == 4 ? k_miller_lines_quad : k_miller_lines_duo, dim3((lg * m + TB_BLOCK - 1) / TB_BLOCK), blk, 0, s,
-                             (const g1a*)P + lo, (const g2a*)Q + lo, (const uint8_t*)skip + lo, ca + lo, cb + lo, m, lines);
-        else
-          hipLaunchKernelGGL(k_miller_lines_w2, dim3((m + TB_BLOCK - 1) / TB_BLOCK), blk, 0, s,
-                             (const g1a*)P + lo, (const g2a*)Q + lo, (const uint8_t*)skip + lo, ca + lo, cb + lo, m, lines);
-        if (settle) continue;  // settle_sets accumulates per set from these lines
-        if (late_join && lo == 0) HIPCHK(hipStreamWaitEvent(s, c.e_join[1], 0));  // the bucket-sum stream first (acc_lds)
-        if (pp.seg()) {
-          const uint32_t g_pad = (mt + TB_BLOCK - 1) / TB_BLOCK * TB_BLOCK;
-          hipLaunchKernelGGL(k_miller_accs_lds, dim3(pp.nseg * g_pad / TB_BLOCK), blk, 0, s,
-                             (const uint4*)lines,
-                             (const uint8_t*)skip + lo,
-                             ca + lo, cb + lo, m, pp.per, pp.nseg, g_pad, f + lo / pp.per, pp.n_groups());
-        } else {
-          hipLaunchKernelGGL(pp.per == 2 ? k_miller_acc2 : k_miller_acc1, dim3((mt + TB_BLOCK - 1) / TB_BLOCK), blk, 0, s,
-                             (const uint4*)lines, (const uint8_t*)skip + lo, ca + lo, cb + lo, m, f + lo / pp.per);
-        }
-      }
-    }
-  }
+    HIPCHK(hipStreamWaitEvent(s, c.e_sig, 0));  // the set pairs' lines read the signature codes; miller() waits for the rest
+  if (const int rc = run.miller()) return rc;
   if (late_join) HIPCHK(hipStreamWaitEvent(s, c.e_join[1], 0));  // every stream joins before ws_release
-  if (settle) {
+  if (o.settle) {
     HIPCHK(hipGetLastError());
     HIPCHK(ws_release(c, s));
     return TBLS_SUCCESS;
   }
   TB_EV(11, s);
-  TB_EV(12, s);
-  if (nf == 0) {  // no pairs at all: the partial product is 1
-    HIPCHK(hipMemsetAsync(w + L.f, 0, sizeof(fp12), s));
-    hipLaunchKernelGGL(k_fp12_one, dim3(1), dim3(64), 0, s, (fp12*)(w + L.f));
-  }
-  {
-    // levels of chunked wave products: f -> fpart -> fpart2 -> fpart ... -> partial_out
-    const fp12* src = (const fp12*)(w + L.f);
-    uint32_t cnt = nf ? nf : 1;
-    int lvl = 0;
-    if (pp.seg() && pp.nseg > 1) {
-      // per segment (grid y), the bit-sum pairs' values with the last, to the
-      // nseg segment products, then the Horner combine into the partial
-      uint32_t cn = pp.n_groups(), cl = pp.n_groups() + pp.n_xwave, stride = pp.n_groups();
-      for (;;) {
-        const uint32_t no = (cn + TB_PROD_CHUNK - 1) / TB_PROD_CHUNK, nl = (cl + TB_PROD_CHUNK - 1) / TB_PROD_CHUNK;
-        const bool fin = nl == 1;
-        fp12* dstp = (fp12*)(w + (fin ? L.segv : ((lvl & 1) ? L.fpart2 : L.fpart)));
-        const uint32_t ostride = fin ? 1u : nl;
-        hipLaunchKernelGGL(k_fp12_prod_wave_seg, dim3(nl, pp.nseg), dim3(64), 0, s, src, cn, cl, pp.nseg, stride, TB_PROD_CHUNK, dstp,
-                           ostride);
-        if (fin) break;
-        src = dstp;
-        cn = no;
-        cl = nl;
-        stride = nl;
-        lvl++;
-      }
-      hipLaunchKernelGGL(k_fp12_seg_combine_coop, dim3(1), dim3(TB_CFE_THREADS), 0, s, (const fp12*)(w + L.segv), pp.nseg,
-                         0u, (fp12*)partial_out);
-    } else
-    for (;;) {
-      const uint32_t pc = prod_chunk(pp), nout = (cnt + pc - 1) / pc;
-      fp12* dstp = nout == 1 ? (fp12*)partial_out : (fp12*)(w + ((lvl & 1) ? L.fpart2 : L.fpart));
-      hipLaunchKernelGGL(k_fp12_prod_wave, dim3(nout), dim3(64), 0, s, src, cnt, pc, dstp);
-      if (nout == 1) break;
-      src = dstp;
-      cnt = nout;
-      lvl++;
-    }
-  }
-  TB_EV(13, s);
-  HIPCHK(hipMemcpyAsync((uint8_t*)partial_out + sizeof(fp12), w + L.n_bad, 4, hipMemcpyDeviceToDevice, s));
+  if (const int rc = run.product_tree(partial_out)) return rc;
+  HIPCHK(hipMemcpyAsync((uint8_t*)partial_out + sizeof(fp12), W.n_bad, 4, hipMemcpyDeviceToDevice, s));
   HIPCHK(hipGetLastError());
   HIPCHK(ws_release(c, s));
   return TBLS_SUCCESS;
 }
+#undef TB_EV
 
 // final: product of g partial records -> final exponentiation, straight from
 // the records (k_final_verify_recs reads them in place; the only device state
@@ -1033,8 +715,11 @@ int shard_launch(dev_ctx* c, const SET* sets, size_t lo, size_t hi, const uint64
   *dpart = di + align_up(p.total);
   *n_out = p.n;
   HIPCHK(hipEventRecord(c->e_t0, s));
-  int rc = launch_partial(*c, b, s, *dpart, L, di + p.off_dst, dlen, nullptr, false, idx_mode ? (const uint32_t*)(di + p.off_pks) : nullptr,
-                          settle, bits_mode ? &cm : nullptr);
+  partial_opts o{di + p.off_dst, dlen};
+  o.key_idx = idx_mode ? (const uint32_t*)(di + p.off_pks) : nullptr;
+  o.settle = settle;
+  o.cm = bits_mode ? &cm : nullptr;
+  int rc = launch_partial(*c, b, s, *dpart, L, o);
   if (rc) return rc;
   HIPCHK(hipEventRecord(c->e_t1, s));
   return TBLS_SUCCESS;
@@ -1100,30 +785,15 @@ int verify_on_device(int d, const SET* sets, size_t n, const uint64_t* rand, con
 //    single sets, whose test is exact.  A set with a failed decode / group /
 //    key check is invalid from its per-set code alone.
 // Batches that ran the bucket-sum signature side (>= 20,480 sets) or the
-// wave Miller loops (<= 1,024 sets) have no per-set signature pairs or no
-// lines: their sets are re-staged in chunks of TB_SETTLE_MAX in the settle
-// layout (pair_plan settle: one signature pair per set, split kernels),
-// which runs the per-set stages and the line kernel only.
+// wave Miller loops (<= 2,048 pairs, a set's two pairs among them: 1,024
+// sets) have no per-set signature pairs or no lines (tb_plan.h
+// settle_ready): their sets are re-staged in chunks of TB_SETTLE_MAX in the
+// settle layout (pair_plan settle: one signature pair per set, split
+// kernels), which runs the per-set stages and the line kernel only.
 // ---------------------------------------------------------------------------
 extern "C" __global__ void k_group_test_coop(const fp12* __restrict__ vals, uint32_t stride, uint32_t nseg, const uint32_t* __restrict__ list,
                                              uint8_t* __restrict__ out);  // k_pair.hip
 extern "C" __global__ void k_settle_mask(const uint8_t* __restrict__ set_code, uint32_t n, uint8_t* __restrict__ skip);  // k_pair.hip
-#define TB_SETTLE_FAN 16u                  // sets per group and groups per group of the next level (k_fp12_prod_wave_seg chunk)
-#define TB_SETTLE_MAX (TB_LINE_CHUNK / 2u)  // sets per settle chunk: both pairs of every set in one line chunk
-
-// segments of the per-set accumulation: fill the GPU once (n threads per segment)
-static uint32_t settle_nseg(uint32_t n) {
-  uint32_t sg = 1;
-  while (sg < 16 && 2ull * sg * n <= TB_ACC_FULL) sg *= 2;
-  return sg;
-}
-
-// true when the pipeline that just ran over n sets left what settle_sets needs:
-// one signature pair per set and both pairs' lines in one chunk
-static bool settle_ready(uint32_t n) {
-  const pair_plan pp(n);
-  return pp.split && !pp.msm && 2ull * n <= TB_LINE_CHUNK;
-}
 
 // Group tests of the listed groups of a segmented value array on c's stream:
 // pass[k] = 1 iff group list[k] tests 1.
@@ -1375,6 +1045,37 @@ struct upload {
   }
 };
 
+// fn(g) for each of G shards: on the calling thread when G == 1, else one host
+// thread per shard (host-side packing and launch queueing in parallel)
+template <class FN>
+void for_each_shard(int G, const FN& fn) {
+  if (G == 1) {
+    fn(0);
+    return;
+  }
+  std::vector<std::thread> th;
+  for (int g = 0; g < G; g++) th.emplace_back(fn, g);
+  for (auto& x : th) x.join();
+}
+
+// The device-resident API's way in: fn(c, s) with device `device` locked and
+// current, s the caller's stream (or the device's own) and the default DST
+// in c.dstb (uploaded on first use).
+template <class FN>
+int with_dev_stream(int device, void* stream, const FN& fn) {
+  if (ensure_init()) return TBLS_DEVICE_ERROR;
+  dev_ctx* c = ctx_for(device);
+  if (!c) return TBLS_DEVICE_ERROR;
+  std::lock_guard<std::mutex> lk(c->mu);
+  const caller_device keep;
+  HIPCHK(hipSetDevice(c->dev));
+  if (!c->dstb.p) {
+    if (c->dstb.ensure(256)) return TBLS_DEVICE_ERROR;
+    HIPCHK(hipMemcpy(c->dstb.p, ETH2_DST, 43, hipMemcpyHostToDevice));
+  }
+  return fn(*c, stream ? (hipStream_t)stream : c->stream);
+}
+
 // one-call helpers run on the least-loaded device (place_one)
 int with_device(const std::function<int(dev_ctx&)>& fn) {
   const caller_device keep;
@@ -1554,18 +1255,11 @@ int batch_verify_impl(const SET* sets, size_t n, const uint64_t* rand, int n_gpu
     for (int g = 0; g < G; g++) locks.emplace_back(ctx_for(pl.dev[g])->mu);
     std::vector<uint8_t*> dpart(G, nullptr);
     std::vector<int> rcs(G, 0);
-    auto stage = [&](int g) {
+    for_each_shard(G, [&](int g) {
       ws_layout L;
       uint32_t nn;
       rcs[g] = shard_launch(ctx_for(pl.dev[g]), sets, pl.cut[g], pl.cut[g + 1], rand, ETH2_DST, 43, &dpart[g], L, &nn);
-    };
-    if (G == 1) {
-      stage(0);
-    } else {  // host-side packing and launch queueing in parallel, one thread per device
-      std::vector<std::thread> th;
-      for (int g = 0; g < G; g++) th.emplace_back(stage, g);
-      for (auto& x : th) x.join();
-    }
+    });
     for (int g = 0; g < G; g++)
       if (rcs[g]) return rcs[g];
     rc = gather_partials(gather_sel(), pl.dev, G, dpart);
@@ -1625,20 +1319,10 @@ extern "C" int tbls_batch_verify_each(const tbls_set* sets_in, size_t n_in, cons
   std::vector<uint8_t*> dpart(G, nullptr);
   std::vector<ws_layout> Ls(G);
   std::vector<int> rcs(G, 0);
-  auto stage = [&](int g) {
+  for_each_shard(G, [&](int g) {
     uint32_t nn;
     rcs[g] = shard_launch(ctx_for(pl.dev[g]), sets.data(), pl.cut[g], pl.cut[g + 1], rand.data(), ETH2_DST, 43, &dpart[g], Ls[g], &nn);
-  };
-  auto run_all = [&](const std::function<void(int)>& fn) {
-    if (G == 1) {
-      fn(0);
-      return;
-    }
-    std::vector<std::thread> th;
-    for (int g = 0; g < G; g++) th.emplace_back(fn, g);
-    for (auto& x : th) x.join();
-  };
-  run_all(stage);
+  });
   for (int g = 0; g < G; g++)
     if (rcs[g]) return rcs[g];
   int rc = TBLS_SUCCESS;
@@ -1663,15 +1347,14 @@ extern "C" int tbls_batch_verify_each(const tbls_set* sets_in, size_t n_in, cons
   }
   std::vector<uint8_t> verdict(n, 1);
   if (!*ok) {
-    auto settle = [&](int g) {
+    for_each_shard(G, [&](int g) {
       dev_ctx* c = ctx_for(pl.dev[g]);
       if (hipSetDevice(c->dev) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
         rcs[g] = TBLS_DEVICE_ERROR;
         return;
       }
       rcs[g] = settle_range(c, sets.data(), pl.cut[g], pl.cut[g + 1], rand.data(), true, Ls[g], verdict.data() + pl.cut[g]);
-    };
-    run_all(settle);
+    });
     for (int g = 0; g < G; g++)
       if (rcs[g]) return rcs[g];
   }
@@ -1778,47 +1461,32 @@ static int run_each(int d, const SET* sets, size_t lo, size_t hi, uint8_t* ok_ho
   HIPCHK(hipMemcpyAsync(c->in.p, c->hin.p, p.total, hipMemcpyHostToDevice, s));
   const uint8_t* di = c->in.as<uint8_t>();
   const uint32_t n = p.n, K = bytes_mode ? p.K : 0u;  // keys to decompress
-  size_t o = 0;
-  const size_t pk_aff = o;   o = align_up(o + (size_t)K * sizeof(g1a));
-  const size_t pk_code = o;  o = align_up(o + (K ? K : 1));
-  const size_t P = o;        o = align_up(o + (size_t)n * sizeof(g1a));
-  const size_t Q = o;        o = align_up(o + (size_t)n * sizeof(g2a));
-  const size_t sig_aff = o;  o = align_up(o + (size_t)n * sizeof(g2a));
-  const size_t skip = o;     o = align_up(o + n);
-  const size_t set_code = o; o = align_up(o + n);
-  const size_t sig_code = o; o = align_up(o + n);
-  const size_t sig_use = o;  o = align_up(o + n);
-  const size_t okd = o;      o = align_up(o + n);
-  const size_t n_bad = o;    o = align_up(o + 4);
-  const size_t mlist = o;    o = align_up(o + (size_t)n * 4 + 4);
-  if (c->ws.ensure(o)) return TBLS_DEVICE_ERROR;
+  const each_layout E(n, K);
+  if (c->ws.ensure(E.total)) return TBLS_DEVICE_ERROR;
   uint8_t* w = c->ws.as<uint8_t>();
+  g1a* P = (g1a*)(w + E.P);
+  g2a *Q = (g2a*)(w + E.Q), *sig_aff = (g2a*)(w + E.sig_aff);
+  uint8_t *skip = w + E.skip, *set_code = w + E.set_code, *sig_code = w + E.sig_code, *sig_use = w + E.sig_use, *okd = w + E.okd;
+  uint32_t* n_bad = (uint32_t*)(w + E.n_bad);
+  const uint64_t* rand = (const uint64_t*)(di + p.off_rand);
+  const key_src keys = bytes_mode ? own_keys((const g1a*)(w + E.pk_aff), w + E.pk_code) : table_keys(*c, (const uint32_t*)(di + p.off_pks));
   const dim3 blk(TB_BLOCK), g((n + TB_BLOCK - 1) / TB_BLOCK);
-  HIPCHK(hipMemsetAsync(w + n_bad, 0, 4, s));
-  HIPCHK(hipMemsetAsync(w + set_code, 0, n, s));  // k_set_pk writes failures only
-  if (K)
-    hipLaunchKernelGGL(k_pk_decompress, dim3((K + TB_BLOCK - 1) / TB_BLOCK), blk, 0, s, di + p.off_pks, K, (g1a*)(w + pk_aff),
-                       w + pk_code);
+  HIPCHK(hipMemsetAsync(n_bad, 0, 4, s));
+  HIPCHK(hipMemsetAsync(set_code, 0, n, s));  // k_set_pk writes failures only
+  if (K) hipLaunchKernelGGL(k_pk_decompress, dim3((K + TB_BLOCK - 1) / TB_BLOCK), blk, 0, s, di + p.off_pks, K, (g1a*)(w + E.pk_aff), w + E.pk_code);
   if constexpr (bits_mode) {
-    if (n)
-      launch_set_pk_bits(s, n, (const uint32_t*)(di + p.off_pks), committee_src(*c, sets[lo].slot), c->tab_aff.as<const g1a>(),
-                         c->tab_code.as<const uint8_t>(), c->tab_n, (const uint64_t*)(di + p.off_rand), (g1a*)(w + P), w + set_code,
-                         (uint32_t*)(w + n_bad), nullptr, nullptr, 1u);
+    if (n) launch_set_pk_bits(s, n, keys, committee_src(*c, sets[lo].slot), rand, P, set_code, n_bad, nullptr, nullptr, 1u);
   } else {
-    launch_set_pk(s, n, p.K, (const uint32_t*)(di + p.off_pkoff), bytes_mode ? (const g1a*)(w + pk_aff) : c->tab_aff.as<const g1a>(),
-                  bytes_mode ? (const uint8_t*)(w + pk_code) : c->tab_code.as<const uint8_t>(), (const uint64_t*)(di + p.off_rand),
-                  (g1a*)(w + P), w + set_code, (uint32_t*)(w + n_bad), bytes_mode ? nullptr : (const uint32_t*)(di + p.off_pks),
-                  bytes_mode ? 0u : c->tab_n, (uint32_t*)(w + mlist), (uint32_t*)(w + mlist) + n, nullptr, nullptr);
+    launch_set_pk(s, n, use_w2(n), multi_key(n, p.K), (const uint32_t*)(di + p.off_pkoff), keys, rand, P, set_code, n_bad, (uint32_t*)(w + E.mlist), (uint32_t*)(w + E.mcnt),
+                  nullptr, nullptr);
   }
-  hipLaunchKernelGGL(k_sig_check, g, blk, 0, s, di + p.off_sigs, n, (g2a*)(w + sig_aff), w + sig_use, w + sig_code, (uint32_t*)(w + n_bad), 0u);
-  hipLaunchKernelGGL(k_set_hash, g, blk, 0, s, di + p.off_msgs, (const uint32_t*)(di + p.off_msgoff), di + p.off_dst, 43u, n, (g2a*)(w + Q),
-                     w + skip);
-  hipLaunchKernelGGL(k_verify_each, g, blk, 0, s, (const g1a*)(w + P), (const g2a*)(w + Q), (const uint8_t*)(w + skip),
-                     (const uint8_t*)(w + set_code), (const g2a*)(w + sig_aff), (const uint8_t*)(w + sig_use),
-                     (const uint8_t*)(w + sig_code), n, w + okd);
+  hipLaunchKernelGGL(k_sig_check, g, blk, 0, s, di + p.off_sigs, n, sig_aff, sig_use, sig_code, n_bad, 0u);
+  hipLaunchKernelGGL(k_set_hash, g, blk, 0, s, di + p.off_msgs, (const uint32_t*)(di + p.off_msgoff), di + p.off_dst, 43u, n, Q, skip);
+  hipLaunchKernelGGL(k_verify_each, g, blk, 0, s, (const g1a*)P, (const g2a*)Q, (const uint8_t*)skip, (const uint8_t*)set_code,
+                     (const g2a*)sig_aff, (const uint8_t*)sig_use, (const uint8_t*)sig_code, n, okd);
   HIPCHK(hipGetLastError());
   if (c->hout.ensure(n)) return TBLS_DEVICE_ERROR;
-  HIPCHK(hipMemcpyAsync(c->hout.p, w + okd, n, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(c->hout.p, okd, n, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   HIPCHK(ws_release(*c, s));
   memcpy(ok_host, c->hout.p, n);
@@ -1840,19 +1508,12 @@ static int verify_each_impl(const SET* sets, size_t n, int n_gpus, int* ok_per_s
   const int G = pl.G;
   std::vector<uint8_t> ok(n, 0);
   std::vector<int> rcs(G, 0);
-  auto work = [&](int k0) {
+  for_each_shard(G, [&](int k0) {
     for (size_t k = k0; k < nchunks && !rcs[k0]; k += G) {
       const size_t lo = k * TB_EACH_CHUNK, hi = std::min(n, lo + TB_EACH_CHUNK);
       rcs[k0] = run_each(pl.dev[k0], sets, lo, hi, ok.data() + lo);
     }
-  };
-  if (G == 1) {
-    work(0);
-  } else {
-    std::vector<std::thread> th;
-    for (int k = 0; k < G; k++) th.emplace_back(work, k);
-    for (auto& x : th) x.join();
-  }
+  });
   for (int k = 0; k < G; k++)
     if (rcs[k]) return rcs[k];
   for (size_t i = 0; i < n; i++) ok_per_set[i] = (sets[i].n_pks != 0 && ok[i]) ? 1 : 0;  // BLS.java:193-195
@@ -1941,9 +1602,8 @@ extern "C" int tbls_committee_load(uint32_t slot, const uint32_t* key_idx, uint3
     // on the direct side with r = 1; an exceptional addition is resolved by
     // the kernel's one-lane body, so only a sum at infinity leaves a code
     bits_src all = {(const uint32_t*)m, (const uint32_t*)(m + TB_CM_OFF_BAD), (const g1a*)(m + TB_CM_OFF_SUM), size, 0u, TB_CM_WORDS};
-    launch_set_pk_bits(s, 1, (const uint32_t*)(m + TB_CM_OFF_VALID), all, c->tab_aff.as<const g1a>(), c->tab_code.as<const uint8_t>(),
-                       c->tab_n, nullptr, (g1a*)(m + TB_CM_OFF_SUM), m + TB_CM_OFF_CODE, (uint32_t*)(m + TB_CM_OFF_CODE + 4), nullptr, nullptr,
-                       1u);
+    launch_set_pk_bits(s, 1, table_keys(*c, (const uint32_t*)(m + TB_CM_OFF_VALID)), all, nullptr, (g1a*)(m + TB_CM_OFF_SUM), m + TB_CM_OFF_CODE,
+                       (uint32_t*)(m + TB_CM_OFF_CODE + 4), nullptr, nullptr, 1u);
     HIPCHK(hipGetLastError());
     uint8_t code = 0xff;
     HIPCHK(hipMemcpyAsync(&code, m + TB_CM_OFF_CODE, 1, hipMemcpyDeviceToHost, s));
@@ -2197,66 +1857,44 @@ extern "C" int tbls_sk_to_pk(const uint8_t sk[32], uint8_t out[48]) {
 }
 
 extern "C" int tbls_dev_batch_partial(int device, const tbls_dev_batch* b, void* stream, void* partial_out) {
-  if (ensure_init()) return TBLS_DEVICE_ERROR;
-  dev_ctx* c = ctx_for(device);
-  if (!c) return TBLS_DEVICE_ERROR;
-  std::lock_guard<std::mutex> lk(c->mu);
-  const caller_device keep;
-  HIPCHK(hipSetDevice(c->dev));
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  if (!c->dstb.p) {
-    if (c->dstb.ensure(256)) return TBLS_DEVICE_ERROR;
-    HIPCHK(hipMemcpy(c->dstb.p, ETH2_DST, 43, hipMemcpyHostToDevice));
-  }
-  ws_layout L;
-  return launch_partial(*c, *b, s, partial_out, L, c->dstb.as<uint8_t>(), 43);
+  return with_dev_stream(device, stream, [&](dev_ctx& c, hipStream_t s) {
+    ws_layout L;
+    return launch_partial(c, *b, s, partial_out, L, partial_opts{c.dstb.as<uint8_t>(), 43});
+  });
 }
 
 extern "C" int tbls_dev_batch_partial_idx(int device, const tbls_dev_batch* b, const uint32_t* key_idx, void* stream, void* partial_out) {
-  if (ensure_init()) return TBLS_DEVICE_ERROR;
-  dev_ctx* c = ctx_for(device);
-  if (!c) return TBLS_DEVICE_ERROR;
-  std::lock_guard<std::mutex> lk(c->mu);
-  const caller_device keep;
-  if (!c->tab_n || !key_idx) return TBLS_BAD_ARGUMENT;
-  HIPCHK(hipSetDevice(c->dev));
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  if (!c->dstb.p) {
-    if (c->dstb.ensure(256)) return TBLS_DEVICE_ERROR;
-    HIPCHK(hipMemcpy(c->dstb.p, ETH2_DST, 43, hipMemcpyHostToDevice));
-  }
-  ws_layout L;
-  return launch_partial(*c, *b, s, partial_out, L, c->dstb.as<uint8_t>(), 43, nullptr, false, key_idx);
+  return with_dev_stream(device, stream, [&](dev_ctx& c, hipStream_t s) -> int {
+    if (!c.tab_n || !key_idx) return TBLS_BAD_ARGUMENT;
+    partial_opts o{c.dstb.as<uint8_t>(), 43};
+    o.key_idx = key_idx;
+    ws_layout L;
+    return launch_partial(c, *b, s, partial_out, L, o);
+  });
 }
 
 static int partial_timed(int device, const tbls_dev_batch* b, void* stream, void* partial_out, float* stage_ms, bool serial) {
-  if (ensure_init()) return TBLS_DEVICE_ERROR;
-  dev_ctx* c = ctx_for(device);
-  if (!c) return TBLS_DEVICE_ERROR;
-  std::lock_guard<std::mutex> lk(c->mu);
-  const caller_device keep;
-  HIPCHK(hipSetDevice(c->dev));
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  if (!c->dstb.p) {
-    if (c->dstb.ensure(256)) return TBLS_DEVICE_ERROR;
-    HIPCHK(hipMemcpy(c->dstb.p, ETH2_DST, 43, hipMemcpyHostToDevice));
-  }
-  hipEvent_t ev[TB_NSTAGE_EV];
-  for (int i = 0; i < TB_NSTAGE_EV; i++) HIPCHK(hipEventCreate(&ev[i]));
-  ws_layout L;
-  int rc = launch_partial(*c, *b, s, partial_out, L, c->dstb.as<uint8_t>(), 43, ev, serial);
-  if (!rc) {
-    HIPCHK(hipEventSynchronize(ev[TB_NSTAGE_EV - 1]));
-    static const int order[TB_NSTAGE] = {0, 1, 2, 3, 4, 5, 6};  // pk, set_pk, set_sig, set_hash, g2_sum, miller, prod
-    const int evi[TB_NSTAGE] = {0, 2, 4, 6, 8, 10, 12};
-    for (int i = 0; i < TB_NSTAGE; i++) {
-      float ms = 0;
-      (void)hipEventElapsedTime(&ms, ev[evi[order[i]]], ev[evi[order[i]] + 1]);
-      stage_ms[i] = ms;
+  return with_dev_stream(device, stream, [&](dev_ctx& c, hipStream_t s) -> int {
+    hipEvent_t ev[TB_NSTAGE_EV];
+    for (int i = 0; i < TB_NSTAGE_EV; i++) HIPCHK(hipEventCreate(&ev[i]));
+    partial_opts o{c.dstb.as<uint8_t>(), 43};
+    o.ev = ev;
+    o.serial = serial;
+    ws_layout L;
+    int rc = launch_partial(c, *b, s, partial_out, L, o);
+    if (!rc) {
+      HIPCHK(hipEventSynchronize(ev[TB_NSTAGE_EV - 1]));
+      static const int order[TB_NSTAGE] = {0, 1, 2, 3, 4, 5, 6};  // pk, set_pk, set_sig, set_hash, g2_sum, miller, prod
+      const int evi[TB_NSTAGE] = {0, 2, 4, 6, 8, 10, 12};
+      for (int i = 0; i < TB_NSTAGE; i++) {
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, ev[evi[order[i]]], ev[evi[order[i]] + 1]);
+        stage_ms[i] = ms;
+      }
     }
-  }
-  for (int i = 0; i < TB_NSTAGE_EV; i++) (void)hipEventDestroy(ev[i]);
-  return rc;
+    for (int i = 0; i < TB_NSTAGE_EV; i++) (void)hipEventDestroy(ev[i]);
+    return rc;
+  });
 }
 
 extern "C" int tbls_dev_batch_partial_timed(int device, const tbls_dev_batch* b, void* stream, void* partial_out, float* stage_ms) {

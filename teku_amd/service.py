@@ -25,7 +25,7 @@ reference sizes its workers to the host's cores (numThreads,
 AggregatingSignatureVerificationService.java:68-69, 121-132; P2PConfig
 .java:42-43), and a large max batch (the device wants >= 16k sets; the
 reference default is 250).  Each worker's batch is placed by the library
-(tb_lib.hip place_plan): with more tasks waiting in the queue the worker
+(tb_plan.h place_plan): with more tasks waiting in the queue the worker
 passes n_gpus = 1, so concurrent batches land on distinct devices, one each;
 a batch that leaves the queue empty may take every idle device, down to 4,096
 sets per device on an idle node (the latency knee).

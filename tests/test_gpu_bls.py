@@ -477,7 +477,7 @@ def test_large_batch_msm_path(hip, n):
 @pytest.mark.parametrize("n", [24576, 32768])
 def test_key_table_bucket_sum_batches(hip, n):
     """Key-table batches large enough for the bucket-sum signature side: the
-    library starts their hash after the signature checks (tb_lib.hip
+    library starts their hash after the signature checks (tb_plan.h
     sig_first, keys from the table) instead of beside them.  Verdicts equal
     the same batches by key bytes (test_large_batch_msm_path's order) for a
     valid batch, a swapped signature, a non-G2 signature and a wrong key

@@ -1,7 +1,7 @@
 """Byte-level parity of the batch hash_to_G2 kernels.
 
-batchVerify hashes with one of five kernels by batch size (tb_lib.hip
-launch_partial, hash_plan(): TB_HASH_ROW_MAX / TB_HASH_QUAD_MAX /
+batchVerify hashes with one of five kernels by batch size (tb_plan.h
+hash_kind, TBLS_HASH_PLAN: TB_HASH_ROW_MAX / TB_HASH_QUAD_MAX /
 TB_HASH_DUO_MAX): k_set_hash_w2 + k_set_hash_fix (> 32,768 sets;
 k_set_hash is its one-wave A/B twin), k_set_hash_duo + k_set_hash_fix
 (8,193 - 32,768),

@@ -1,7 +1,7 @@
 """Sharded batches and per-shard settling on one GPU (ADVICE round 5,
 medium): tools/shared_devices_probe.py initialises the library with
 TBLS_INIT_SHARE_DEVICES (two library devices over the one MI355X), so a lone
-batch on the idle "node" is sharded (tb_lib.hip place_plan, the 4,096-set
+batch on the idle "node" is sharded (tb_plan.h place_plan, the 4,096-set
 knee), the two partial records are gathered, and a failed batch is settled on
 both devices concurrently at the per-shard offsets (tbls_batch_verify_each
 settle_range).  Verdicts must equal the C oracle's per-set

@@ -1,4 +1,4 @@
-"""Device placement of batches (tb_lib.hip place_plan through tbls_place_plan;
+"""Device placement of batches (tb_plan.h place_plan through tbls_place_plan;
 pure host logic, no device): a batch is sharded only over IDLE devices and
 only into shards of at least shard_min = 32,768 sets (where one device's
 partial stops being a latency chain, profiles/r04_stage_sweep_final.json);
@@ -164,7 +164,7 @@ def test_bad_arguments():
 
 @pytest.mark.parametrize("n,plan", [(131072, (16, 8)), (16384, (8, 16)), (1048576, (16, 4)), (3000, (2, 16))])
 def test_accumulator_plan(n, plan):
-    """tb_lib.hip acc_plan (tbls_acc_plan, no device): the segmented Miller
+    """tb_plan.h acc_plan (tbls_acc_plan, no device): the segmented Miller
     accumulator's pairs per thread x loop segments for the bench batch
     (131,072 sets: one 65,536-thread wave round of 16 x 8), config 4
     (16,384 sets, per-set signature pairs: 32,768 pairs, 8 x 16), 1,048,576 sets (262,144-pair
