@@ -18,6 +18,7 @@ extern "C" __global__ void __launch_bounds__(TB_BLOCK) k_test_ops(int op, const 
   (void)test_op_a(op, in + (size_t)i * TB_TEST_IN, out + (size_t)i * TB_TEST_OUT);
 }
 extern "C" __global__ void k_test_ops_b(int op, const uint8_t* in, uint8_t* out, uint32_t n);  // k_test_b.hip
+extern "C" __global__ void k_test_ops_c(int op, const uint8_t* in, uint8_t* out, uint32_t n);  // k_test_c.hip
 
 // test hook: one final exponentiation per 64-lane block (tb_testops.h record layout)
 extern "C" __global__ void __launch_bounds__(64) k_test_final_exp_wave(const uint8_t* in, uint8_t* out) {
@@ -190,6 +191,8 @@ extern "C" int tbls_test_ops(int op, const uint8_t* in, uint8_t* out, size_t n) 
       hipLaunchKernelGGL(k_test_clear_cof_prog, dim3((uint32_t)n), dim3(64), 0, 0, din, dout);
     else if (test_op_in_a(op))
       hipLaunchKernelGGL(k_test_ops, dim3((uint32_t)((n + TB_BLOCK - 1) / TB_BLOCK)), dim3(TB_BLOCK), 0, 0, op, din, dout, (uint32_t)n);
+    else if (test_op_in_c(op))
+      hipLaunchKernelGGL(k_test_ops_c, dim3((uint32_t)((n + TB_BLOCK - 1) / TB_BLOCK)), dim3(TB_BLOCK), 0, 0, op, din, dout, (uint32_t)n);
     else
       hipLaunchKernelGGL(k_test_ops_b, dim3((uint32_t)((n + TB_BLOCK - 1) / TB_BLOCK)), dim3(TB_BLOCK), 0, 0, op, din, dout, (uint32_t)n);
     if (hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&

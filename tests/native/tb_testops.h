@@ -9,6 +9,7 @@
 #pragma once
 #include "../../teku_amd/csrc/tb_stages.h"
 #include "../../teku_amd/csrc/tb_cinv.h"
+#include "../../teku_amd/csrc/tb_glv.h"
 
 namespace tb {
 
@@ -56,6 +57,23 @@ enum {
   // the row inversion (tb_cinv.h) -- host emulation only (the GPU form is the
   // per-row k_test_coop_inv, op 47)
   TOP_FP_INV_ROW = 38,
+  // 39..55: the wave / coop kernels of k_test.hip and k_test_coop.hip
+  // Fr (tb_fr.h) and the GLV scalar multiplication (tb_glv.h) of the KZG
+  // kernels; scalars are 32-byte big-endian plain integers (test_op_c)
+  TOP_FR_ADD = 56,
+  TOP_FR_SUB = 57,
+  TOP_FR_MUL = 58,
+  TOP_FR_SQR = 59,
+  TOP_FR_NEG = 60,
+  // plain limbs in (any 256-bit a, b), the raw limbs of fr_mul out: no
+  // Montgomery conversion on either side (fr_from_digest's contract)
+  TOP_FR_MUL_RAW = 61,
+  TOP_FR_INV = 62,
+  TOP_FR_POW_U32 = 63,      // a || e (u32 little-endian)
+  TOP_FR_FROM_BYTES = 64,   // out = u32 canonical flag || fr_to_be of the value when canonical
+  TOP_FR_FROM_DIGEST = 65,  // any 256-bit value in, fr_to_be(fr_from_digest) out
+  TOP_GLV_SPLIT = 66,       // k < r in, a || b (16 bytes big-endian each) out
+  TOP_G1_MUL_FR = 67,       // P affine (x || y) || k in, u32 finite flag || affine [k]P out
 };
 
 #define TB_TEST_IN 1536
@@ -110,8 +128,26 @@ TB_HD TB_INLINE void tio_put_raw(uint8_t* b, const fp& r) {
   fp_plain_to_be(r, b + 48);
 }
 
-// The ops in two halves, one device kernel each (tests/native/k_test.hip,
-// k_test_b.hip: two translation units compiled in parallel); inlined into the
+TB_HD TB_INLINE fr tio_fr(const uint8_t* b) { return fr_to_mont(fr_plain_from_be(b)); }
+// an Fr result: 32 bytes big-endian, then one byte: 1 when the limbs as
+// computed are fully reduced (< r), which fr_to_be's own product would hide
+TB_HD TB_INLINE void tio_put_fr(uint8_t* b, const fr& a) {
+  fr_to_be(b, a);
+  b[32] = fr_geq_mod(a.l) ? 0 : 1;
+}
+// plain limbs -> 32 bytes big-endian, no conversion
+TB_HD TB_INLINE void tio_put_fr_plain(uint8_t* b, const fr& p) {
+  for (int i = 0; i < 8; i++) {
+    uint8_t* q = b + 28 - 4 * i;
+    q[0] = (uint8_t)(p.l[i] >> 24);
+    q[1] = (uint8_t)(p.l[i] >> 16);
+    q[2] = (uint8_t)(p.l[i] >> 8);
+    q[3] = (uint8_t)p.l[i];
+  }
+}
+
+// The ops in three parts, one device kernel each (tests/native/k_test.hip,
+// k_test_b.hip, k_test_c.hip: translation units compiled in parallel); inlined into the
 // kernels -- as an outlined function of this size the long-branch expansion of
 // ROCm 7.2's clang would go through the return address (tools/check_long_branches.py).
 // Field, tower and pairing ops:
@@ -331,6 +367,73 @@ TB_HD TB_INLINE bool test_op_b(int op, const uint8_t* in, uint8_t* out) {
   return true;
 }
 
+// Fr and GLV ops (the KZG kernels' scalar side):
+TB_HD TB_INLINE bool test_op_c(int op, const uint8_t* in, uint8_t* out) {
+  switch (op) {
+    case TOP_FR_ADD:
+      tio_put_fr(out, fr_add(tio_fr(in), tio_fr(in + 32)));
+      break;
+    case TOP_FR_SUB:
+      tio_put_fr(out, fr_sub(tio_fr(in), tio_fr(in + 32)));
+      break;
+    case TOP_FR_MUL:
+      tio_put_fr(out, fr_mul(tio_fr(in), tio_fr(in + 32)));
+      break;
+    case TOP_FR_SQR:
+      tio_put_fr(out, fr_sqr(tio_fr(in)));
+      break;
+    case TOP_FR_NEG:
+      tio_put_fr(out, fr_neg(tio_fr(in)));
+      break;
+    case TOP_FR_MUL_RAW:
+      tio_put_fr_plain(out, fr_mul(fr_plain_from_be(in), fr_plain_from_be(in + 32)));
+      break;
+    case TOP_FR_INV:
+      tio_put_fr(out, fr_inv(tio_fr(in)));
+      break;
+    case TOP_FR_POW_U32:
+      tio_put_fr(out, fr_pow_u32(tio_fr(in), tio_u32(in + 32)));
+      break;
+    case TOP_FR_FROM_BYTES: {
+      fr v;
+      const bool ok = fr_from_canonical(v, fr_plain_from_be(in));
+      tio_put_u32(out, ok ? 1u : 0u);
+      if (ok) fr_to_be(out + 4, v);
+      break;
+    }
+    case TOP_FR_FROM_DIGEST:
+      tio_put_fr(out, fr_from_digest(fr_plain_from_be(in)));
+      break;
+    case TOP_GLV_SPLIT: {
+      uint32_t a[4], b[4];
+      glv_split(fr_plain_from_be(in), a, b);
+      fr lo = fr_zero();
+      for (int i = 0; i < 4; i++) {
+        lo.l[i] = b[i];
+        lo.l[4 + i] = a[i];
+      }
+      tio_put_fr_plain(out, lo);  // a in the high 16 bytes, b in the low
+      break;
+    }
+    case TOP_G1_MUL_FR: {
+      const g1a P = {tio_fp(in), tio_fp(in + 48)};
+      g1a a;
+      const bool fin = jac_to_aff(a, g1_mul_fr(P, tio_fr(in + 96)));
+      tio_put_u32(out, fin ? 1u : 0u);
+      if (fin) {
+        tio_put_fp(out + 4, a.x);
+        tio_put_fp(out + 52, a.y);
+      }
+      break;
+    }
+    default:
+      return false;
+  }
+  return true;
+}
+
+TB_HD TB_INLINE bool test_op_in_c(int op) { return op >= TOP_FR_ADD && op <= TOP_G1_MUL_FR; }
+
 TB_HD TB_INLINE bool test_op_in_a(int op) {
   return op == TOP_FP_MUL || op == TOP_FP_INV || op == TOP_FP2_MUL || op == TOP_FP2_SQRT || op == TOP_FP12_MUL || op == TOP_FP12_CYC_SQR ||
          op == TOP_FP12_FROB || op == TOP_FINAL_EXP || op == TOP_MILLER || op == TOP_FP12_SQR || op == TOP_FP12_INV || op == TOP_FP_SQR ||
@@ -338,9 +441,9 @@ TB_HD TB_INLINE bool test_op_in_a(int op) {
          op == TOP_FP2_SQR_RAW;
 }
 
-// both halves (the host build, tests/native/hostsim.cpp)
+// every part (the host build, tests/native/hostsim.cpp)
 TB_HD TB_INLINE void test_op(int op, const uint8_t* in, uint8_t* out) {
-  if (!test_op_a(op, in, out)) (void)test_op_b(op, in, out);
+  if (!test_op_a(op, in, out) && !test_op_b(op, in, out)) (void)test_op_c(op, in, out);
 }
 
 }  // namespace tb

@@ -19,6 +19,7 @@ OPS = dict(
     MILLER=9, G1_DECOMP=10, G2_DECOMP=11, HASH_TO_G2=12, G1_IN_GROUP=13, G2_IN_GROUP=14, SSWU=15,
     ISO=16, CLEAR_COF=17, FP12_SQR=18, FP12_INV=19, HASH_TO_FIELD=20, FP_SQR=21, FP_ADD=22, FP_SUB=23, FINAL_EXP_WAVE=29, MILLER2=30, MILLER_WAVE=31, MILLER_PROG=40, CLEAR_COF_PROG=41, WAVE_TIMING=42, COOP_MUL=43, COOP_TIMING=44, COOP_INV=47, FP_INV_ROW=38, FINAL_EXP_COOP=45, CFE_OPS=46,
     COOP_MUL_DIGITS=48, COOP_MUL_WORDS=49, COOP_TO_FP=50, COOP_REDUCE=51, COOP_INV_RAW=52, COOP_INV_U=53, COOP_POINT_G1=54, COOP_POINT_G2=55,
+    FR_ADD=56, FR_SUB=57, FR_MUL=58, FR_SQR=59, FR_NEG=60, FR_MUL_RAW=61, FR_INV=62, FR_POW_U32=63, FR_FROM_BYTES=64, FR_FROM_DIGEST=65, GLV_SPLIT=66, G1_MUL_FR=67,
     FP_MUL_RAW=32, FP_SQR_RAW=33, FP2_MUL_RAW=34, FP2_SQR_RAW=35, CLEAR_COF_NX=36, G2_IN_GROUP_NX=37, STAGE_PK=24, STAGE_SET_PK=25, STAGE_SET_SIG=26, STAGE_SET_HASH=27, G2_JADD=28,
 )
 
@@ -150,3 +151,26 @@ def load_test_lib():
     L.tbls_test_ops.restype = ctypes.c_int
     L.tbls_test_ops.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
     return L
+
+
+KZG_REC = 100  # tests/native/k_test_kzg.hip output record
+
+
+def kzg_kernel_runner(L):
+    """run(stage, coop, in_bytes, n, n_out) -> n_out records of KZG_REC bytes from
+    tbls_test_kzg_kernel (tests/native/k_test_kzg.hip): the product library's
+    own k_kzg_points / k_kzg_terms kernels in the one-lane (coop = 0) or the
+    lane-cooperative form (coop = 1)."""
+    from teku_amd import native
+
+    fn = L.tbls_test_kzg_kernel
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_void_p]
+
+    def run(stage, coop, data, n, n_out):
+        out = ctypes.create_string_buffer(KZG_REC * n_out)
+        rc = fn(native.LIB_PATH.encode(), stage, coop, bytes(data), n, out)
+        assert rc == 0, rc
+        return [out.raw[KZG_REC * i : KZG_REC * (i + 1)] for i in range(n_out)]
+
+    return run

@@ -190,3 +190,78 @@ def test_many_blobs_batch(ckzg, orc):
     ps2 = list(ps)
     ps2[17], ps2[18] = ps[18], ps[17]
     assert ckzg.verify_blob_kzg_proof_batch(blobs, cs, ps2) is False
+
+
+# ---- edge inputs through the public API -------------------------------------
+MU = 0xD201000000010000**2  # the GLV eigenvalue (tb_glv.h): multiples of it take glv_split's correction
+
+
+def _edge_zs():
+    roots = K.roots_brp()
+    return roots, [0, 1, BLS_MODULUS - 1, roots[255], roots[256], roots[4095], MU, 5 * MU]
+
+
+@pytest.mark.parametrize("kind", ["random", "all r-1", "zero"])
+def test_proofs_at_edge_points(ckzg, orc, kind):
+    """compute_kzg_proof / verify_kzg_proof at z = 0, domain points (1 and
+    r - 1 = -1 among them) and multiples of mu, for a random blob, the constant
+    r - 1 (a zero quotient: the proof is infinity) and the zero blob (commitment
+    and proof at infinity): proof and y equal the C oracle's and verify."""
+    blob = {"random": sample_blob(31), "all r-1": blob_of([BLS_MODULUS - 1] * 4096), "zero": blob_of([0] * 4096)}[kind]
+    roots, zs = _edge_zs()
+    c = ckzg.blob_to_kzg_commitment(blob)
+    assert c == orc.blob_to_kzg_commitment(blob)
+    for zi in zs:
+        z = zi.to_bytes(32, "big")
+        proof, y = ckzg.compute_kzg_proof(blob, z)
+        assert (proof, y) == orc.compute_kzg_proof(blob, z), hex(zi)
+        if zi in roots:
+            i = roots.index(zi)
+            assert y == blob[32 * i:32 * i + 32], hex(zi)
+        assert ckzg.verify_kzg_proof(c, z, y, proof) is True, hex(zi)
+    assert sum(z in roots for z in zs) == 5  # 1, r - 1 and the three named roots are domain points
+
+
+@pytest.mark.parametrize("pos", [0, 255, 256, 4095])
+def test_noncanonical_elements_at_block_edges(ckzg, orc, pos):
+    """A field element r, r + 1 or 2^256 - 1 in the first or last element and on
+    both sides of a 256-element thread stride is C_KZG_BADARGS in every call
+    that reads the blob; r - 1 there is accepted."""
+    base = sample_blob(32)
+    put = lambda v: base[:32 * pos] + v.to_bytes(32, "big") + base[32 * pos + 32:]  # noqa: E731
+    good = put(BLS_MODULUS - 1)
+    c = ckzg.blob_to_kzg_commitment(good)
+    assert c == orc.blob_to_kzg_commitment(good)
+    p = ckzg.compute_blob_kzg_proof(good, c)
+    assert ckzg.verify_blob_kzg_proof(good, c, p) is True
+    for v in (BLS_MODULUS, BLS_MODULUS + 1, (1 << 256) - 1):
+        bad = put(v)
+        for call in [lambda: ckzg.blob_to_kzg_commitment(bad), lambda: ckzg.verify_blob_kzg_proof(bad, c, p)]:
+            with pytest.raises(kzg.KZGException) as ei:
+                call()
+            assert ei.value.__cause__.error == kzg.C_KZG_BADARGS, (hex(v), pos)
+        with pytest.raises(kzg.CKZGException) as ei:
+            ckzg.compute_kzg_proof(bad, (5).to_bytes(32, "big"))
+        assert ei.value.error == kzg.C_KZG_BADARGS, (hex(v), pos)
+
+
+def test_constructed_relation_with_chosen_scalars(ckzg):
+    """p(x) = x^2: the commitment is [tau^2]G1 (the setup's g1_monomial[2]),
+    y = z^2 and the proof commits to (x^2 - z^2) / (x - z) = x + z, that is
+    g1_monomial[1] + [z]G1.  The check then multiplies the proof by z and -G1
+    by y = z^2, two different edge scalars per call, for every scalar of the
+    GLV edge list (0, multiples of mu, r - 1, ...)."""
+    from oracle import bls12_381 as O
+    from tests.kzg_cases import g1_mul, mul_scalars
+
+    ts = kzg.parse_trusted_setup_file(SETUP)
+    code, tau1 = O.g1_decompress(ts.g1_monomial[1])
+    assert code == O.SUCCESS
+    c = ts.g1_monomial[2]
+    for zi in mul_scalars():
+        zg = g1_mul(O.G1_GEN, zi)
+        proof = O.g1_compress(O.jac_to_affine(O.FP, O.jac_add(O.FP, O.jac_from_affine(O.FP, tau1), O.jac_from_affine(O.FP, zg))))
+        z, y = zi.to_bytes(32, "big"), (zi * zi % BLS_MODULUS).to_bytes(32, "big")
+        assert ckzg.verify_kzg_proof(c, z, y, proof) is True, hex(zi)
+        y1 = ((zi * zi + 1) % BLS_MODULUS).to_bytes(32, "big")
+        assert ckzg.verify_kzg_proof(c, z, y1, proof) is False, hex(zi)
