@@ -143,7 +143,10 @@ typedef struct {
  * device is idle (tbls_place_plan); each device produces one Fp12
  * partial product, gathered for one final exponentiation.  *ok = 1 iff every set is valid and the pairing product is
  * 1.  n == 0 -> *ok = 0 (BLS.java:240-241).  A set with n_pks == 0 ->
- * TBLS_BAD_ARGUMENT (BlstPublicKey.aggregate checkArgument, l.56). */
+ * TBLS_BAD_ARGUMENT (BlstPublicKey.aggregate checkArgument, l.56).
+ * With a key table loaded (tbls_pk_table_load), keys that the table holds are
+ * taken from it by their bytes instead of being decompressed again; the
+ * verdict is the same. */
 int tbls_batch_verify(const tbls_set* sets, size_t n, const uint64_t* rand, int n_gpus, int* ok, tbls_timing* t);
 
 /* ---- device-resident validator public-key table ----
@@ -156,9 +159,43 @@ int tbls_batch_verify(const tbls_set* sets, size_t n, const uint64_t* rand, int 
  * device (96-byte affine + status per key in HBM) and batches name keys by
  * index, so no key bytes travel and no key is decompressed per call.
  * Replaces any previous table.  codes (nullable, K bytes): per-key status as
- * tbls_pk_validate (TBLS_SUCCESS, TBLS_PK_IS_INFINITY, ...). */
+ * tbls_pk_validate (TBLS_SUCCESS, TBLS_PK_IS_INFINITY, ...).
+ *
+ * The load also keeps the K compressed keys on every device and builds an
+ * index over their bytes (an open-addressing hash table keyed by a seed drawn
+ * at each load; a reload rebuilds it from empty).  Callers that name keys by
+ * their bytes -- tbls_batch_verify, tbls_batch_verify_each, tbls_verify_each,
+ * tbls_fast_aggregate_verify_many, tbls_dev_batch_partial -- then have each
+ * key looked up first: a key whose 48 bytes equal a table key's takes the
+ * table's point and status, any other key is decompressed and checked as
+ * without a table.  The results are the same either way: the table's entry
+ * was computed from the same bytes by the same kernel.  (Single-key batches
+ * of up to 512 sets decode their keys inside their one key kernel and do not
+ * look them up.)  TBLS_PK_LOOKUP=0 in the environment, read by tbls_init,
+ * turns the index off: no keys are kept, no index is built, byte keys are
+ * always decompressed and tbls_pk_table_resolve finds no index. */
 int tbls_pk_table_load(const uint8_t* pks, size_t K, uint8_t* codes);
 size_t tbls_pk_table_size(void);
+
+/* Drop the table, its index and every resident committee on every device
+ * (tbls_pk_table_size() becomes 0; the lookup counters are zeroed). */
+int tbls_pk_table_clear(void);
+
+/* The table index of each of n keys given by their bytes, in one device pass:
+ * idx_out[i] is an index whose table key equals pks[48 i .. 48 i + 48) byte for
+ * byte (of equal table keys, any one), or 0xFFFFFFFF when the table holds no
+ * such key.  An integration memoizes the index in its public-key object and
+ * moves to the index entries (tbls_batch_verify_idx, ...).  No table (or no
+ * index, TBLS_PK_LOOKUP=0) -> TBLS_BAD_ARGUMENT.  Not counted in
+ * tbls_pk_lookup_stats. */
+int tbls_pk_table_resolve(const uint8_t* pks, size_t n, uint32_t* idx_out);
+
+/* out[0] = keys the batch key stages took from the table, out[1] = keys they
+ * looked up and did not find (and decompressed), since the last table load or
+ * reset, summed over the devices; each device's counters are read under its
+ * lock after its stream is synchronised.  reset != 0 zeroes them after
+ * reading.  Both stay 0 without a table and with TBLS_PK_LOOKUP=0. */
+int tbls_pk_lookup_stats(uint64_t out[2], int reset);
 
 /* A signature set whose keys are table indices (the unit of
  * BLS.prepareBatchVerify, BLS.java:353-368, with keys by validator index). */

@@ -72,6 +72,32 @@ final class HipPublicKey implements PublicKey {
     return bytes;
   }
 
+  // The index of these bytes in the resident key table (tbls_pk_table_resolve),
+  // memoized per table generation: the caller counts a generation up at every
+  // pkTableLoad, since an index means a position in one loaded table.
+  // TekuBlsHipPkIndex.MISS (-1): the table does not hold this key.  A batch
+  // verifier resolves many keys in one call and stores each answer with
+  // rememberTableIndex; this single-key form is the fallback.
+  private volatile long tableIndexMemo = Long.MIN_VALUE; // generation << 32 | index
+
+  int tableIndex(final int generation) {
+    final long m = tableIndexMemo;
+    if (m != Long.MIN_VALUE && (int) (m >> 32) == generation) {
+      return (int) m;
+    }
+    final int[] idx = new int[1];
+    final int rc = TekuBlsHipPkIndex.pkTableResolve(bytes, idx);
+    if (rc != TekuBlsHip.SUCCESS) {
+      return TekuBlsHipPkIndex.MISS; // no table: stay on the byte-keyed entries
+    }
+    rememberTableIndex(generation, idx[0]);
+    return idx[0];
+  }
+
+  void rememberTableIndex(final int generation, final int index) {
+    tableIndexMemo = ((long) generation << 32) | (index & 0xffffffffL);
+  }
+
   boolean isInfinity() {
     return Arrays.equals(bytes, INFINITY);
   }

@@ -570,6 +570,41 @@ class ValidatorKeyTable:
         native.check(rc, "tbls_fast_aggregate_verify_many_idx")
         return [bool(out[i]) for i in range(n)]
 
+    MISS = 0xFFFFFFFF
+
+    def resolve(self, keys) -> List[int]:
+        """The table index of each 48-byte key (tbls_pk_table_resolve, one
+        device pass): an index whose table key has the same bytes, or
+        ValidatorKeyTable.MISS for a key the table does not hold.  A caller
+        memoizes the index with its key object and names the key by index from
+        then on.  Raises ValueError when no table (or no index) is loaded."""
+        n = len(keys)
+        blob = b"".join(bytes(k) for k in keys)
+        if len(blob) != 48 * n:
+            raise ValueError("a public key is 48 bytes")
+        out = (ctypes.c_uint32 * max(1, n))()
+        rc = native.lib().tbls_pk_table_resolve(blob or b"\0", n, out)
+        if rc == native.BAD_ARGUMENT:
+            raise ValueError("no key table / no key index")
+        native.check(rc, "tbls_pk_table_resolve")
+        return list(out[:n])
+
+    @staticmethod
+    def lookup_stats(reset=False):
+        """(hits, misses) of the byte-keyed batches' key lookups since the
+        table was loaded or the counters were last reset, over all devices
+        (tbls_pk_lookup_stats)."""
+        out = (ctypes.c_uint64 * 2)()
+        native.check(native.lib().tbls_pk_lookup_stats(out, 1 if reset else 0), "tbls_pk_lookup_stats")
+        return int(out[0]), int(out[1])
+
+    def clear(self):
+        """Drop the table, its index and the committees on every device
+        (tbls_pk_table_clear)."""
+        native.check(native.lib().tbls_pk_table_clear(), "tbls_pk_table_clear")
+        self.size = 0
+        self.codes = []
+
     def load_committee(self, slot, indices) -> "Committee":
         """Make the committee `indices` (validator indices into this table,
         duplicates allowed) resident in `slot` on every device."""

@@ -24,6 +24,7 @@
 #include "tb_kdecl_mid.h"
 #include "tb_hrow.h"
 #include "tb_host.h"
+#include "tb_pkindex.h"  // the key table's index over its key bytes: hash, probe step, probe bound
 #include "tb_plan.h"  // every host-side decision: kernel choice, pair split, product levels, workspace layout, placement
 
 static_assert(TB_PARTIAL_BYTES == TBLS_PARTIAL_BYTES, "partial record size");
@@ -62,6 +63,11 @@ struct dbuf {
     cap = nb;
     return 0;
   }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
   template <typename T>
   T* as(size_t off = 0) const {
     return reinterpret_cast<T*>(static_cast<uint8_t*>(p) + off);
@@ -94,6 +100,15 @@ struct dev_ctx {
   hipStream_t aux[3] = {nullptr, nullptr, nullptr};  // concurrent per-set stages (aux[1] signatures + bucket sums, aux[2] hash_to_G2: high priority)
   dbuf tab_aff, tab_code;                    // device-resident public-key table (tbls_pk_table_load)
   uint32_t tab_n = 0;
+  // The table's index over its compressed key bytes (tb_pkindex.h, built by
+  // tbls_pk_table_load unless TBLS_PK_LOOKUP=0): the K keys as loaded, the
+  // slots (pkx_cap of them, 0: no index) and the load's hash seed.  pkx_stat:
+  // hits and misses of the batch key stages (two 64-bit words).  pkx_miss:
+  // the key stage's miss list, count first (K + 1 words for a batch of K
+  // keys); used between ws_acquire and ws_release like `ws`, and grown like it.
+  dbuf tab_keys, pkx_slots, pkx_stat, pkx_miss;
+  uint32_t pkx_cap = 0;
+  uint64_t pkx_seed = 0;
   // resident committees (tbls_committee_load): per slot TB_CM_STRIDE bytes of
   // cmt (members, bad-member mask, valid-member row, the valid members' sum,
   // the load pass's code and failure count); size 0: empty slot
@@ -120,6 +135,7 @@ inline hipError_t ws_release(dev_ctx& c, hipStream_t s) { return hipEventRecord(
 std::mutex g_mu;
 std::vector<dev_ctx*> g_ctx;
 bool g_inited = false;
+bool g_pk_lookup = true;  // TBLS_PK_LOOKUP=0 (read by tbls_init): no index, byte keys are always decompressed (A/B, parity tests)
 
 uint32_t shard_min() { return plan_env::get().shard_min; }
 uint32_t shard_knee() { return plan_env::get().shard_knee; }
@@ -297,6 +313,60 @@ extern "C" __global__ void k_keys_coop(const uint8_t* __restrict__ pks, const ui
 extern "C" __global__ void k_sig_check_coop(const uint8_t* __restrict__ sigs, uint32_t n, g2a* __restrict__ sig_aff, uint8_t* __restrict__ sig_use,
                                             uint8_t* __restrict__ sig_code, uint32_t* __restrict__ n_bad);  // k_kcoop.hip
 
+// k_pkindex.hip
+extern "C" __global__ void k_pkx_build(const uint32_t* __restrict__ keys, uint32_t K, uint32_t* slots, uint32_t mask, uint64_t seed);
+extern "C" __global__ void k_pk_lookup(const uint8_t* __restrict__ pks, uint32_t K, uint32_t align, const uint32_t* __restrict__ slots,
+                                       uint32_t mask, uint64_t seed, const uint32_t* __restrict__ tab_keys, const g1a* __restrict__ tab_aff,
+                                       const uint8_t* __restrict__ tab_code, g1a* __restrict__ pk_aff, uint8_t* __restrict__ pk_code,
+                                       uint32_t* __restrict__ miss, unsigned long long* __restrict__ stat);
+extern "C" __global__ void k_pk_decompress_list(const uint8_t* __restrict__ pks, const uint32_t* __restrict__ list, g1a* __restrict__ pk_aff,
+                                                uint8_t* __restrict__ pk_code);
+extern "C" __global__ void k_pk_resolve(const uint8_t* __restrict__ pks, uint32_t n, uint32_t align, const uint32_t* __restrict__ slots,
+                                        uint32_t mask, uint64_t seed, const uint32_t* __restrict__ tab_keys, uint32_t* __restrict__ idx_out);
+#define TB_PKX_BLOCK 256u
+
+// The widest loads a key array at p allows (k_pkindex.hip pkx_load_key).
+inline uint32_t pkx_align(const void* p) {
+  const uintptr_t a = (uintptr_t)p;
+  return !(a & 15u) ? 16u : !(a & 3u) ? 4u : 1u;
+}
+
+// True when byte keys on c resolve from the table's index first.
+inline bool pk_lookup_on(const dev_ctx& c) { return c.tab_n && c.pkx_cap; }
+
+// Room for the miss list of a K-key stage; the caller holds the workspace
+// (ws_acquire) and `s` orders every earlier user of it, so growing drains s
+// first, as the workspace does.
+int pk_lookup_reserve(dev_ctx& c, uint32_t K, hipStream_t s) {
+  const size_t need = ((size_t)K + 1) * 4;
+  if (!pk_lookup_on(c) || need <= c.pkx_miss.cap) return TBLS_SUCCESS;
+  HIPCHK(hipStreamSynchronize(s));
+  return c.pkx_miss.ensure(need) ? TBLS_DEVICE_ERROR : TBLS_SUCCESS;
+}
+
+// The key stage of K byte keys: affine points and validity codes into pk_aff /
+// pk_code.  With a table index on the device (pk_lookup_on, pk_lookup_reserve
+// called) it is two steps: launch_pk_lookup -- k_pk_lookup copies the keys the
+// table knows and lists the others -- then launch_pk_decompress with `listed`
+// -- k_pk_decompress_list decompresses that list.  The same bytes give the
+// same point and code either way, since the table's entries came from
+// k_pk_decompress.  Without an index: k_pk_decompress over all K.
+int launch_pk_lookup(dev_ctx& c, hipStream_t s, const uint8_t* pks, uint32_t K, g1a* pk_aff, uint8_t* pk_code) {
+  uint32_t* miss = c.pkx_miss.as<uint32_t>();
+  HIPCHK(hipMemsetAsync(miss, 0, 4, s));
+  hipLaunchKernelGGL(k_pk_lookup, dim3((K + TB_PKX_BLOCK - 1) / TB_PKX_BLOCK), dim3(TB_PKX_BLOCK), 0, s, pks, K, pkx_align(pks),
+                     c.pkx_slots.as<const uint32_t>(), c.pkx_cap - 1u, c.pkx_seed, c.tab_keys.as<const uint32_t>(), c.tab_aff.as<const g1a>(),
+                     c.tab_code.as<const uint8_t>(), pk_aff, pk_code, miss, c.pkx_stat.as<unsigned long long>());
+  return TBLS_SUCCESS;
+}
+void launch_pk_decompress(dev_ctx& c, hipStream_t s, const uint8_t* pks, uint32_t K, g1a* pk_aff, uint8_t* pk_code, bool listed) {
+  const dim3 blk(TB_BLOCK), g((K + TB_BLOCK - 1) / TB_BLOCK);
+  if (listed)  // the grid covers K: the list's length is only known on the device
+    hipLaunchKernelGGL(k_pk_decompress_list, g, blk, 0, s, pks, c.pkx_miss.as<const uint32_t>(), pk_aff, pk_code);
+  else
+    hipLaunchKernelGGL(k_pk_decompress, g, blk, 0, s, pks, K, pk_aff, pk_code);
+}
+
 // One launch_partial call: the batch, its plan, the workspace and the streams
 // of its chains.  Each chain queues on one stream, in order; launch_partial
 // forks and joins them.
@@ -309,6 +379,10 @@ struct partial_run {
   const key_src& keys;
   hipStream_t s, sa, sb, sh;  // the caller's, keys, signatures + bucket sums, hash
   bool late_join;             // bp.late_join with the streams side by side
+  // Byte keys on a device with a table index (pk_lookup_on): look the keys up
+  // first.  pre_lookup: launch_partial has queued the lookup on the caller's
+  // stream ahead of the fork, and the key stream starts at the misses.
+  bool lookup, pre_lookup;
   const uint32_t n = b.n;
   const dim3 blk = dim3(TB_BLOCK), g = dim3((b.n + TB_BLOCK - 1) / TB_BLOCK);  // one thread per set
   g1a* sig_P() const { return bp.pp.msm ? nullptr : W.P + n; }                 // -[r_i] g1 of the sets' signature pairs
@@ -354,7 +428,7 @@ struct partial_run {
   // --- stream a: public keys, [r] apk (+ -[r] g1 for the signature pairs) -----
   int key_chain() const {
     const g1a* comb = c.comb.as<const g1a>();
-    TB_EV(0, sa);
+    if (!pre_lookup) TB_EV(0, sa);  // else recorded before the lookup (launch_partial)
     if (bp.key == key_kind::bits) {
       TB_EV(1, sa);
       TB_EV(2, sa);
@@ -366,8 +440,9 @@ struct partial_run {
       TB_EV(1, sa);
       TB_EV(2, sa);
     } else {
-      if (bp.n_keys)
-        hipLaunchKernelGGL(k_pk_decompress, dim3((bp.n_keys + TB_BLOCK - 1) / TB_BLOCK), blk, 0, sa, b.pks, bp.n_keys, W.pk_aff, W.pk_code);
+      if (lookup && !pre_lookup)
+        if (const int rc = launch_pk_lookup(c, sa, b.pks, bp.n_keys, W.pk_aff, W.pk_code)) return rc;
+      if (bp.n_keys) launch_pk_decompress(c, sa, b.pks, bp.n_keys, W.pk_aff, W.pk_code, lookup);  // the keys the table does not hold, or all
       TB_EV(1, sa);
       TB_EV(2, sa);
       launch_set_pk(sa, n, bp.w2, bp.multi, b.pk_off, keys, b.rand, W.P, W.set_code, W.n_bad, W.mlist, W.mcnt, sig_P(), comb);
@@ -493,6 +568,8 @@ int launch_partial(dev_ctx& c, const tbls_dev_batch& b, hipStream_t s, void* par
     HIPCHK(hipStreamSynchronize(s));
     if (c.ws.ensure(L.total)) return TBLS_DEVICE_ERROR;
   }
+  if (bp.key == key_kind::decompress)
+    if (const int rc = pk_lookup_reserve(c, bp.n_keys, s)) return rc;
   const ws_ptrs W(L, c.ws.as<uint8_t>());
   const key_src keys = o.key_idx ? table_keys(c, o.key_idx) : own_keys(W.pk_aff, W.pk_code);
   // `serial` (tbls_dev_batch_stage_profile): every stage on the caller's
@@ -504,9 +581,25 @@ int launch_partial(dev_ctx& c, const tbls_dev_batch& b, hipStream_t s, void* par
   // partial unchanged, 32,768 sets 14.16 -> 12.44 ms, 65,536 26.11 -> 22.23,
   // 131,072 37.73 -> 36.15, profiles/r04_stage_chain_ab.json.)
   const bool late_join = bp.late_join && !o.serial;
-  const partial_run run{c, b, o, bp, W, keys, s, o.serial ? s : c.aux[0], o.serial ? s : c.aux[1], o.serial ? s : c.aux[2], late_join};
+  // Whether byte keys are looked up is decided here, at launch, inside the
+  // plan's decompress branch.  The lookup (k_pk_lookup, tens of microseconds)
+  // is queued on the caller's stream ahead of the fork, and the key stream
+  // starts at the decompression of the misses, as it starts at the
+  // decompression of all keys without a table.  Queued as the first kernel of
+  // the key stream instead, a 16,384-set batch through tbls_batch_verify took
+  // 10.5 ms with every key in the table and 12.2 ms with none, against 8.9 ms
+  // without a table, although no stage's own time grew; ahead of the fork: 8.9,
+  // 9.0, 8.8.  `serial` keeps the lookup inside the key stage's
+  // bracket, for the exclusive stage times.
+  const bool lookup = bp.key == key_kind::decompress && bp.n_keys && pk_lookup_on(c);
+  const partial_run run{c, b, o, bp, W, keys, s, o.serial ? s : c.aux[0], o.serial ? s : c.aux[1], o.serial ? s : c.aux[2], late_join,
+                        lookup, lookup && !o.serial};
   HIPCHK(hipMemsetAsync(W.set_code, 0, 2 * align_up(bp.pp.n_pairs), s));  // set_code and sig_code (adjacent)
   HIPCHK(hipMemsetAsync(W.n_bad, 0, 4, s));
+  if (run.pre_lookup) {
+    if (o.ev) HIPCHK(hipEventRecord(o.ev[0], s));  // stage 0 starts here
+    if (const int rc = launch_pk_lookup(c, s, b.pks, bp.n_keys, W.pk_aff, W.pk_code)) return rc;
+  }
   if (!o.serial) {
     HIPCHK(hipEventRecord(c.e_fork, s));
     HIPCHK(hipStreamWaitEvent(run.sa, c.e_fork, 0));
@@ -1156,6 +1249,7 @@ extern "C" int tbls_init(int n_devices, uint32_t flags) {
     return TBLS_DEVICE_ERROR;
   }
   const int hw = count;
+  g_pk_lookup = !(getenv("TBLS_PK_LOOKUP") && getenv("TBLS_PK_LOOKUP")[0] == '0');
   if ((flags & TBLS_INIT_SHARE_DEVICES) && n_devices > 0 && n_devices <= 32)
     count = n_devices;  // contexts over the hardware devices round-robin
   else if (n_devices > 0 && n_devices < count)
@@ -1211,6 +1305,7 @@ extern "C" void tbls_shutdown(void) {
     if (c->tab_aff.p) (void)hipFree(c->tab_aff.p);
     if (c->tab_code.p) (void)hipFree(c->tab_code.p);
     if (c->cmt.p) (void)hipFree(c->cmt.p);
+    for (dbuf* b : {&c->tab_keys, &c->pkx_slots, &c->pkx_stat, &c->pkx_miss}) b->release();
     if (c->hin.p) (void)hipHostFree(c->hin.p);
     if (c->hout.p) (void)hipHostFree(c->hout.p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1376,10 +1471,15 @@ extern "C" int tbls_pk_table_load(const uint8_t* pks, size_t K, uint8_t* codes) 
   if (ensure_init()) return TBLS_DEVICE_ERROR;
   if (K == 0 || K > 0xffffffffu / 96) return TBLS_BAD_ARGUMENT;
   std::vector<dev_ctx*> devs;
+  bool index;
   {
     std::lock_guard<std::mutex> lk(g_mu);
     devs = g_ctx;
+    index = g_pk_lookup;
   }
+  uint64_t seed = 0;  // of this load's index: from the OS entropy source, as the randomizers
+  if (index && fill_random(&seed, 1)) return TBLS_DEVICE_ERROR;
+  const uint32_t cap = tb::pkx_capacity((uint32_t)K);
   for (size_t d = 0; d < devs.size(); d++) {
     dev_ctx* c = devs[d];
     std::lock_guard<std::mutex> lk(c->mu);
@@ -1388,6 +1488,7 @@ extern "C" int tbls_pk_table_load(const uint8_t* pks, size_t K, uint8_t* codes) 
     HIPCHK(ws_acquire(*c, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->tab_n = 0;
+    c->pkx_cap = 0;                          // and no index until this load's is complete
     for (uint32_t& sz : c->cm_size) sz = 0;  // the committees' indices meant the old table
     if (c->in.ensure(K * 48) || c->tab_aff.ensure(K * sizeof(g1a)) || c->tab_code.ensure(K)) return TBLS_DEVICE_ERROR;
     HIPCHK(hipMemcpyAsync(c->in.p, pks, K * 48, hipMemcpyHostToDevice, c->stream));
@@ -1395,8 +1496,90 @@ extern "C" int tbls_pk_table_load(const uint8_t* pks, size_t K, uint8_t* codes) 
                        c->in.as<const uint8_t>(), (uint32_t)K, c->tab_aff.as<g1a>(), c->tab_code.as<uint8_t>());
     HIPCHK(hipGetLastError());
     if (d == 0 && codes) HIPCHK(hipMemcpyAsync(codes, c->tab_code.p, K, hipMemcpyDeviceToHost, c->stream));
+    if (index) {
+      // the keys stay resident beside their points, and every slot is cleared:
+      // nothing of an earlier table's index survives.  The stream is
+      // synchronised below, under the lock, before any lookup can run.
+      if (c->tab_keys.ensure(K * 48) || c->pkx_slots.ensure((size_t)cap * 4) || c->pkx_stat.ensure(16)) return TBLS_DEVICE_ERROR;
+      HIPCHK(hipMemcpyAsync(c->tab_keys.p, c->in.p, K * 48, hipMemcpyDeviceToDevice, c->stream));
+      HIPCHK(hipMemsetAsync(c->pkx_slots.p, 0, (size_t)cap * 4, c->stream));
+      HIPCHK(hipMemsetAsync(c->pkx_stat.p, 0, 16, c->stream));
+      hipLaunchKernelGGL(k_pkx_build, dim3((uint32_t)((K + TB_PKX_BLOCK - 1) / TB_PKX_BLOCK)), dim3(TB_PKX_BLOCK), 0, c->stream,
+                         c->tab_keys.as<const uint32_t>(), (uint32_t)K, c->pkx_slots.as<uint32_t>(), cap - 1u, seed);
+      HIPCHK(hipGetLastError());
+    }
     HIPCHK(hipStreamSynchronize(c->stream));
     c->tab_n = (uint32_t)K;
+    if (index) {
+      c->pkx_seed = seed;
+      c->pkx_cap = cap;
+    }
+  }
+  return TBLS_SUCCESS;
+}
+
+// Drop the table, its index and the committees on every device.
+extern "C" int tbls_pk_table_clear(void) {
+  const caller_device keep;
+  if (ensure_init()) return TBLS_DEVICE_ERROR;
+  std::vector<dev_ctx*> devs;
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    devs = g_ctx;
+  }
+  for (dev_ctx* c : devs) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->dev));
+    HIPCHK(ws_acquire(*c, c->stream));  // device-API partials on a caller's stream may still read the table
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->tab_n = 0;
+    c->pkx_cap = 0;
+    for (uint32_t& sz : c->cm_size) sz = 0;
+    for (dbuf* b : {&c->tab_aff, &c->tab_code, &c->tab_keys, &c->pkx_slots, &c->cmt}) b->release();
+    if (c->pkx_stat.p) HIPCHK(hipMemset(c->pkx_stat.p, 0, 16));
+  }
+  return TBLS_SUCCESS;
+}
+
+// One device pass over n keys: the table index of each key's bytes.
+extern "C" int tbls_pk_table_resolve(const uint8_t* pks, size_t n, uint32_t* idx_out) {
+  if (n && (!pks || !idx_out)) return TBLS_BAD_ARGUMENT;
+  if (n > 0xffffffffu / 48) return TBLS_BAD_ARGUMENT;
+  return with_device([&](dev_ctx& c) -> int {
+    if (!pk_lookup_on(c)) return (int)TBLS_BAD_ARGUMENT;  // no table (or no index: TBLS_PK_LOOKUP=0)
+    if (!n) return (int)TBLS_SUCCESS;
+    const size_t o_idx = align_up(n * 48);
+    if (c.in.ensure(o_idx + n * 4)) return (int)TBLS_DEVICE_ERROR;
+    HIPCHK(hipMemcpyAsync(c.in.p, pks, n * 48, hipMemcpyHostToDevice, c.stream));
+    hipLaunchKernelGGL(k_pk_resolve, dim3((uint32_t)((n + TB_PKX_BLOCK - 1) / TB_PKX_BLOCK)), dim3(TB_PKX_BLOCK), 0, c.stream,
+                       c.in.as<const uint8_t>(), (uint32_t)n, pkx_align(c.in.p), c.pkx_slots.as<const uint32_t>(), c.pkx_cap - 1u, c.pkx_seed,
+                       c.tab_keys.as<const uint32_t>(), c.in.as<uint32_t>(o_idx));
+    return fetch(c, idx_out, c.in.as<uint8_t>(o_idx), n * 4);
+  });
+}
+
+// Hits and misses of the batch key stages' lookups, summed over the devices.
+extern "C" int tbls_pk_lookup_stats(uint64_t out[2], int reset) {
+  const caller_device keep;
+  if (!out) return TBLS_BAD_ARGUMENT;
+  out[0] = out[1] = 0;
+  if (ensure_init()) return TBLS_DEVICE_ERROR;
+  std::vector<dev_ctx*> devs;
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    devs = g_ctx;
+  }
+  for (dev_ctx* c : devs) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->pkx_stat.p) continue;
+    HIPCHK(hipSetDevice(c->dev));
+    HIPCHK(ws_acquire(*c, c->stream));  // key stages queued on a caller's stream count too
+    uint64_t v[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(v, c->pkx_stat.p, 16, hipMemcpyDeviceToHost, c->stream));
+    if (reset) HIPCHK(hipMemsetAsync(c->pkx_stat.p, 0, 16, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    out[0] += v[0];
+    out[1] += v[1];
   }
   return TBLS_SUCCESS;
 }
@@ -1463,6 +1646,7 @@ static int run_each(int d, const SET* sets, size_t lo, size_t hi, uint8_t* ok_ho
   const uint32_t n = p.n, K = bytes_mode ? p.K : 0u;  // keys to decompress
   const each_layout E(n, K);
   if (c->ws.ensure(E.total)) return TBLS_DEVICE_ERROR;
+  if (const int rc = pk_lookup_reserve(*c, K, s)) return rc;
   uint8_t* w = c->ws.as<uint8_t>();
   g1a* P = (g1a*)(w + E.P);
   g2a *Q = (g2a*)(w + E.Q), *sig_aff = (g2a*)(w + E.sig_aff);
@@ -1473,7 +1657,12 @@ static int run_each(int d, const SET* sets, size_t lo, size_t hi, uint8_t* ok_ho
   const dim3 blk(TB_BLOCK), g((n + TB_BLOCK - 1) / TB_BLOCK);
   HIPCHK(hipMemsetAsync(n_bad, 0, 4, s));
   HIPCHK(hipMemsetAsync(set_code, 0, n, s));  // k_set_pk writes failures only
-  if (K) hipLaunchKernelGGL(k_pk_decompress, dim3((K + TB_BLOCK - 1) / TB_BLOCK), blk, 0, s, di + p.off_pks, K, (g1a*)(w + E.pk_aff), w + E.pk_code);
+  if (K) {  // byte keys: from the table's index where it holds them, the others (or all) decompressed
+    const bool lookup = pk_lookup_on(*c);
+    if (lookup)
+      if (const int rc = launch_pk_lookup(*c, s, di + p.off_pks, K, (g1a*)(w + E.pk_aff), w + E.pk_code)) return rc;
+    launch_pk_decompress(*c, s, di + p.off_pks, K, (g1a*)(w + E.pk_aff), w + E.pk_code, lookup);
+  }
   if constexpr (bits_mode) {
     if (n) launch_set_pk_bits(s, n, keys, committee_src(*c, sets[lo].slot), rand, P, set_code, n_bad, nullptr, nullptr, 1u);
   } else {

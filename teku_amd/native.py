@@ -155,6 +155,9 @@ _SIGS = {
     "tbls_dev_batch_partial": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(TblsDevBatch), ctypes.c_void_p, ctypes.c_void_p]),
     "tbls_pk_table_load": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p]),
     "tbls_pk_table_size": (ctypes.c_size_t, []),
+    "tbls_pk_table_clear": (ctypes.c_int, []),
+    "tbls_pk_table_resolve": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32)]),
+    "tbls_pk_lookup_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
     "tbls_batch_verify_idx": (
         ctypes.c_int,
         [
