@@ -55,8 +55,9 @@ __device__ TB_INLINE jac<F> jac_mul_u256(const jac<F>& P, const uint64_t* k) {
   return r;
 }
 
-// Kernel declarations (definitions in k_keys / k_sigs / k_hash / k_pair / k_test .hip),
-// for the host code in tb_lib.hip.
+// Kernel declarations (definitions in the k_*.hip translation units), for the
+// host code in tb_lib.hip.  Every defining file includes this header, so a
+// definition whose parameters differ from its prototype does not compile.
 extern "C" __global__ void k_pk_decompress(const uint8_t* __restrict__ pks, uint32_t K, g1a* __restrict__ pk_aff, uint8_t* __restrict__ pk_code);
 extern "C" __global__ void k_set_pk(const uint32_t* __restrict__ pk_off, const g1a* __restrict__ pk_aff, const uint8_t* __restrict__ pk_code, const uint64_t* __restrict__ rand, uint32_t n, g1a* __restrict__ P, uint8_t* __restrict__ set_code, uint32_t* __restrict__ n_bad, const uint32_t* __restrict__ key_idx, uint32_t tab_n, uint32_t multi_wave, g1a* __restrict__ P2, const g1a* __restrict__ comb);
 extern "C" __global__ void k_multi_list(const uint32_t* __restrict__ pk_off, uint32_t n, uint32_t* __restrict__ list, uint32_t* __restrict__ cnt);
@@ -114,3 +115,38 @@ inline void tb_launch_final_recs(const uint8_t* recs, uint32_t g, hipStream_t s,
 // resident committees (k_kcoop.hip): the bad-member mask, and [r] apk of sets given as participation bit rows
 extern "C" __global__ void k_committee_mask(const uint32_t* __restrict__ members, uint32_t size, const uint8_t* __restrict__ tab_code, uint32_t tab_n, uint32_t* __restrict__ bad, uint32_t* __restrict__ valid);
 extern "C" __global__ void k_set_pk_bits_coop(const uint32_t* __restrict__ rows, uint32_t stride_w, const uint32_t* __restrict__ members, uint32_t size, const uint32_t* __restrict__ bad, const g1a* __restrict__ csum, uint32_t sum_ok, const g1a* __restrict__ tab_aff, const uint8_t* __restrict__ tab_code, uint32_t tab_n, const uint64_t* __restrict__ rand, uint32_t n, g1a* __restrict__ P, uint8_t* __restrict__ set_code, uint32_t* __restrict__ n_bad, g1a* __restrict__ P2, const g1a* __restrict__ comb, uint32_t unit_r);
+// k_lines.hip: the segmented accumulator with f in LDS and two lines per
+// product (tb_lines.h miller_accs_lds_body).  Measured at 131,072 sets
+// (profiles/r05_bench_acc_lds_ab.json): Miller stage alone 13.3 -> 12.6 ms
+// and scratch writes 3.3 -> 1.5 GB per launch.  Its grid is one round of
+// workgroups at full LDS (4 x 36,864 B per CU), so a workgroup of the
+// bucket-sum stream still resident on a CU pushes part of it into a second
+// round: beside that stream the 131k step went 38.2 -> 43.9 ms.  So the
+// bucket sums run on a high-priority stream (the signature stream, created
+// at the hash stream's priority in tbls_init) and the accumulator waits for
+// that stream: with both, the LDS kernel runs at every batch size -- 131k
+// step 37.3 -> 36.1-36.6 ms (profiles/r05_bench_prio_join.json; the two
+// were A/B switches in round 5, TBLS_SIG_PRIO / TBLS_ACC_JOIN).  Round 6
+// removed the register-resident k_miller_accs and its TBLS_ACC_LDS switch.
+extern "C" __global__ void k_miller_accs_lds(const uint4* __restrict__ lines, const uint8_t* __restrict__ skip, const uint8_t* __restrict__ code_a, const uint8_t* __restrict__ code_b, uint32_t n, uint32_t per, uint32_t nseg, uint32_t g_pad, fp12* __restrict__ f_out, uint32_t seg_stride);
+extern "C" __global__ void k_msm_bucket_tree(const g2a* __restrict__ sig_aff, const uint8_t* __restrict__ use, const uint32_t* __restrict__ off, const uint32_t* __restrict__ idx, g2j* __restrict__ bucket);  // k_sigs.hip
+// one workgroup per set (k_hwave.hip): the cofactor clearing lane-parallel, and the lane-cooperative form (256 threads)
+extern "C" __global__ void k_set_hash_wave(const uint8_t* __restrict__ msgs, const uint32_t* __restrict__ msg_off, const uint8_t* __restrict__ dst, uint32_t dlen, uint32_t n, g2a* __restrict__ Q, uint8_t* __restrict__ skip);
+extern "C" __global__ void k_set_hash_coop(const uint8_t* __restrict__ msgs, const uint32_t* __restrict__ msg_off, const uint8_t* __restrict__ dst, uint32_t dlen, uint32_t n, g2a* __restrict__ Q, uint8_t* __restrict__ skip, const uint64_t* __restrict__ rand);
+// the small batches' key and signature stages, lane-cooperative (k_kcoop.hip)
+extern "C" __global__ void k_keys_coop(const uint8_t* __restrict__ pks, const uint32_t* __restrict__ pk_off, const g1a* __restrict__ tab_aff, const uint8_t* __restrict__ tab_code, const uint32_t* __restrict__ key_idx, uint32_t tab_n, const uint64_t* __restrict__ rand, uint32_t n, g1a* __restrict__ P, g1a* __restrict__ P2, uint8_t* __restrict__ set_code, uint32_t* __restrict__ n_bad, const g1a* __restrict__ comb);
+extern "C" __global__ void k_sig_check_coop(const uint8_t* __restrict__ sigs, uint32_t n, g2a* __restrict__ sig_aff, uint8_t* __restrict__ sig_use, uint8_t* __restrict__ sig_code, uint32_t* __restrict__ n_bad);
+// the key table's index over its key bytes (k_pkindex.hip; workgroups of its TB_PKX_BLOCK threads)
+extern "C" __global__ void k_pkx_build(const uint32_t* __restrict__ keys, uint32_t K, uint32_t* slots, uint32_t mask, uint64_t seed);
+extern "C" __global__ void k_pk_lookup(const uint8_t* __restrict__ pks, uint32_t K, uint32_t align, const uint32_t* __restrict__ slots, uint32_t mask, uint64_t seed, const uint32_t* __restrict__ tab_keys, const g1a* __restrict__ tab_aff, const uint8_t* __restrict__ tab_code, g1a* __restrict__ pk_aff, uint8_t* __restrict__ pk_code, uint32_t* __restrict__ miss, unsigned long long* __restrict__ stat);
+extern "C" __global__ void k_pk_decompress_list(const uint8_t* __restrict__ pks, const uint32_t* __restrict__ list, g1a* __restrict__ pk_aff, uint8_t* __restrict__ pk_code);
+extern "C" __global__ void k_pk_resolve(const uint8_t* __restrict__ pks, uint32_t n, uint32_t align, const uint32_t* __restrict__ slots, uint32_t mask, uint64_t seed, const uint32_t* __restrict__ tab_keys, uint32_t* __restrict__ idx_out);
+// settling a failed batch (k_pair.hip; tb_lib.hip settle_sets)
+extern "C" __global__ void k_group_test_coop(const fp12* __restrict__ vals, uint32_t stride, uint32_t nseg, const uint32_t* __restrict__ list, uint8_t* __restrict__ out);
+extern "C" __global__ void k_settle_mask(const uint8_t* __restrict__ set_code, uint32_t n, uint8_t* __restrict__ skip);
+// lane-group cooperative mid-size kernels (k_hquad.hip): one DPP quad / one lane pair per set or pair; the one-lane line kernel at two waves per SIMD (k_w2_lines.hip)
+extern "C" __global__ void k_set_hash_quad(const uint8_t* __restrict__ msgs, const uint32_t* __restrict__ msg_off, const uint8_t* __restrict__ dst, uint32_t dlen, uint32_t n, g2a* __restrict__ Q, uint8_t* __restrict__ skip);
+extern "C" __global__ void k_miller_lines_quad(const g1a* __restrict__ P, const g2a* __restrict__ Q, const uint8_t* __restrict__ skip, const uint8_t* __restrict__ code_a, const uint8_t* __restrict__ code_b, uint32_t n, uint4* __restrict__ lines);
+extern "C" __global__ void k_set_hash_duo(const uint8_t* __restrict__ msgs, const uint32_t* __restrict__ msg_off, const uint8_t* __restrict__ dst, uint32_t dlen, uint32_t n, g2a* __restrict__ Q, uint8_t* __restrict__ skip);
+extern "C" __global__ void k_miller_lines_duo(const g1a* __restrict__ P, const g2a* __restrict__ Q, const uint8_t* __restrict__ skip, const uint8_t* __restrict__ code_a, const uint8_t* __restrict__ code_b, uint32_t n, uint4* __restrict__ lines);
+extern "C" __global__ void k_miller_lines_w2(const g1a* __restrict__ P, const g2a* __restrict__ Q, const uint8_t* __restrict__ skip, const uint8_t* __restrict__ code_a, const uint8_t* __restrict__ code_b, uint32_t n, uint4* __restrict__ lines);

@@ -21,11 +21,11 @@
 
 #include "../../include/tekubls.h"
 #include "tb_kdecl.h"
-#include "tb_kdecl_mid.h"
 #include "tb_hrow.h"
 #include "tb_host.h"
 #include "tb_pkindex.h"  // the key table's index over its key bytes: hash, probe step, probe bound
 #include "tb_plan.h"  // every host-side decision: kernel choice, pair split, product levels, workspace layout, placement
+#include "tb_pack.h"  // the staging image of a host batch: set kinds, layout, fill
 
 static_assert(TB_PARTIAL_BYTES == TBLS_PARTIAL_BYTES, "partial record size");
 static_assert(tb::plan::LINE_BYTES_PER_PAIR == TB_LINE_BYTES_PER_PAIR, "tb_plan.h: line bytes per pair");
@@ -33,6 +33,7 @@ static_assert(tb::plan::HROW_SET_BYTES == sizeof(tb::hrow_set), "tb_plan.h: row-
 
 using tb::caller_device;
 using namespace tb::plan;
+using namespace tb::pack;
 
 namespace {
 
@@ -50,21 +51,29 @@ hipError_t& last_hip_error() {
   return e;
 }
 
-struct dbuf {
+// A growable buffer in device memory (HOST false) or pinned host memory, freed
+// with its owner.  Growing frees the old block: the caller has drained its users.
+template <bool HOST>
+struct gbuf {
   void* p = nullptr;
   size_t cap = 0;
+  gbuf() = default;
+  gbuf(const gbuf&) = delete;
+  gbuf& operator=(const gbuf&) = delete;
+  ~gbuf() { release(); }
   int ensure(size_t bytes) {
     if (bytes <= cap) return 0;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t nb = bytes < 4096 ? 4096 : bytes + bytes / 4;
-    if (hipMalloc(&p, nb) != hipSuccess) return -1;
+    release();
+    const size_t nb = bytes < 4096 ? 4096 : bytes + bytes / 4;
+    if ((HOST ? hipHostMalloc(&p, nb, hipHostMallocDefault) : hipMalloc(&p, nb)) != hipSuccess) {
+      p = nullptr;
+      return -1;
+    }
     cap = nb;
     return 0;
   }
   void release() {
-    if (p) (void)hipFree(p);
+    if (p) (void)(HOST ? hipHostFree(p) : hipFree(p));
     p = nullptr;
     cap = 0;
   }
@@ -73,23 +82,11 @@ struct dbuf {
     return reinterpret_cast<T*>(static_cast<uint8_t*>(p) + off);
   }
 };
+using dbuf = gbuf<false>;
+using hbuf = gbuf<true>;
 
-struct hbuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  int ensure(size_t bytes) {
-    if (bytes <= cap) return 0;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t nb = bytes < 4096 ? 4096 : bytes + bytes / 4;
-    if (hipHostMalloc(&p, nb, hipHostMallocDefault) != hipSuccess) return -1;
-    cap = nb;
-    return 0;
-  }
-  uint8_t* b() const { return static_cast<uint8_t*>(p); }
-};
-
+// One library device: its streams, events and buffers, all owned -- created by
+// init() or on first use, released by the destructor.
 struct dev_ctx {
   int dev = 0;
   hipStream_t stream = nullptr;
@@ -125,6 +122,36 @@ struct dev_ctx {
   dbuf comb;  // (d 2^(8w)) g1 for w < 8, d < 256 (k_g1_comb_init): the signature pairs' G1 side
   hbuf hin, hout;
   int load = 0;  // batches placed on this device and not yet finished (g_place_mu)
+
+  dev_ctx() = default;
+  dev_ctx(const dev_ctx&) = delete;
+  dev_ctx& operator=(const dev_ctx&) = delete;
+  // The streams (signatures and hash at high priority), the events and the
+  // comb table on hardware device hw; false: the context is to be deleted.
+  bool init(int hw) {
+    const auto ok = [](hipError_t e) { return e == hipSuccess; };
+    const auto event = [&](hipEvent_t* e) { return ok(hipEventCreateWithFlags(e, hipEventDisableTiming)); };
+    dev = hw;
+    int prio_lo = 0, prio_hi = 0;
+    if (!(ok(hipSetDevice(dev)) && ok(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)) &&
+          ok(hipStreamCreateWithFlags(&aux[0], hipStreamNonBlocking)) && ok(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi)) &&
+          ok(hipStreamCreateWithPriority(&aux[1], hipStreamNonBlocking, prio_hi)) &&
+          ok(hipStreamCreateWithPriority(&aux[2], hipStreamNonBlocking, prio_hi)) && event(&e_join[2]) && event(&e_fork) && event(&e_join[0]) &&
+          event(&e_join[1]) && event(&e_sig) && event(&e_ws) && ok(hipEventCreate(&e_t0)) && ok(hipEventCreate(&e_t1)) &&
+          !comb.ensure(TB_MSM_BUCKETS * sizeof(g1a))))
+      return false;
+    hipLaunchKernelGGL(k_g1_comb_init, dim3(TB_MSM_BUCKETS / TB_BLOCK), dim3(TB_BLOCK), 0, stream, comb.as<g1a>());
+    return ok(hipGetLastError()) && ok(hipStreamSynchronize(stream));
+  }
+  // With the context's device current: the handles init() got as far as, then
+  // (as members) every buffer.
+  ~dev_ctx() {
+    (void)hipSetDevice(dev);
+    for (hipStream_t s : {stream, aux[0], aux[1], aux[2]})
+      if (s) (void)hipStreamDestroy(s);
+    for (hipEvent_t e : {e_fork, e_join[0], e_join[1], e_join[2], e_sig, e_t0, e_t1, e_ws})
+      if (e) (void)hipEventDestroy(e);
+  }
 };
 
 // Order a new user of c.ws (on stream s) after the previous one; call
@@ -265,7 +292,6 @@ struct bits_src {
   const g1a* sum;
   uint32_t size, sum_ok, stride_w;
 };
-inline uint32_t bits_stride_w(uint32_t size) { return (size + 31u) / 32u; }  // the (size + 7) / 8 bytes, rounded to 4
 inline bits_src committee_src(const dev_ctx& c, uint32_t slot) {
   const uint8_t* m = c.cmt.as<const uint8_t>((size_t)slot * TB_CM_STRIDE);
   return {(const uint32_t*)m, (const uint32_t*)(m + TB_CM_OFF_BAD), (const g1a*)(m + TB_CM_OFF_SUM), c.cm_size[slot], c.cm_sum_ok[slot],
@@ -282,48 +308,7 @@ void launch_set_pk_bits(hipStream_t s, uint32_t n, const key_src& ks, const bits
                      cm.sum, cm.sum_ok, ks.aff, ks.code, ks.tab_n, rand, n, P, set_code, n_bad, P2, comb, unit_r);
 }
 
-// k_lines.hip: the segmented accumulator with f in LDS and two lines per
-// product (tb_lines.h miller_accs_lds_body).  Measured at 131,072 sets
-// (profiles/r05_bench_acc_lds_ab.json): Miller stage alone 13.3 -> 12.6 ms
-// and scratch writes 3.3 -> 1.5 GB per launch.  Its grid is one round of
-// workgroups at full LDS (4 x 36,864 B per CU), so a workgroup of the
-// bucket-sum stream still resident on a CU pushes part of it into a second
-// round: beside that stream the 131k step went 38.2 -> 43.9 ms.  So the
-// bucket sums run on a high-priority stream (the signature stream, created
-// at the hash stream's priority in tbls_init) and the accumulator waits for
-// that stream: with both, the LDS kernel runs at every batch size -- 131k
-// step 37.3 -> 36.1-36.6 ms (profiles/r05_bench_prio_join.json; the two
-// were A/B switches in round 5, TBLS_SIG_PRIO / TBLS_ACC_JOIN).  Round 6
-// removed the register-resident k_miller_accs and its TBLS_ACC_LDS switch.
-extern "C" __global__ void k_miller_accs_lds(const uint4* __restrict__ lines, const uint8_t* __restrict__ skip, const uint8_t* __restrict__ code_a,
-                                             const uint8_t* __restrict__ code_b, uint32_t n, uint32_t per, uint32_t nseg, uint32_t g_pad,
-                                             fp12* __restrict__ f_out, uint32_t seg_stride);
-extern "C" __global__ void k_msm_bucket_tree(const g2a* __restrict__ sig_aff, const uint8_t* __restrict__ use, const uint32_t* __restrict__ off,
-                                             const uint32_t* __restrict__ idx, g2j* __restrict__ bucket);  // k_sigs.hip
-extern "C" __global__ void k_set_hash_wave(const uint8_t* __restrict__ msgs, const uint32_t* __restrict__ msg_off,
-                                           const uint8_t* __restrict__ dst, uint32_t dlen, uint32_t n, g2a* __restrict__ Q,
-                                           uint8_t* __restrict__ skip);  // k_hwave.hip
-extern "C" __global__ void k_set_hash_coop(const uint8_t* __restrict__ msgs, const uint32_t* __restrict__ msg_off,
-                                           const uint8_t* __restrict__ dst, uint32_t dlen, uint32_t n, g2a* __restrict__ Q,
-                                           uint8_t* __restrict__ skip, const uint64_t* __restrict__ rand);  // k_hwave.hip (lane-cooperative, 256 threads)
-extern "C" __global__ void k_keys_coop(const uint8_t* __restrict__ pks, const uint32_t* __restrict__ pk_off, const g1a* __restrict__ tab_aff,
-                                       const uint8_t* __restrict__ tab_code, const uint32_t* __restrict__ key_idx, uint32_t tab_n,
-                                       const uint64_t* __restrict__ rand, uint32_t n, g1a* __restrict__ P, g1a* __restrict__ P2,
-                                       uint8_t* __restrict__ set_code, uint32_t* __restrict__ n_bad, const g1a* __restrict__ comb);
-extern "C" __global__ void k_sig_check_coop(const uint8_t* __restrict__ sigs, uint32_t n, g2a* __restrict__ sig_aff, uint8_t* __restrict__ sig_use,
-                                            uint8_t* __restrict__ sig_code, uint32_t* __restrict__ n_bad);  // k_kcoop.hip
-
-// k_pkindex.hip
-extern "C" __global__ void k_pkx_build(const uint32_t* __restrict__ keys, uint32_t K, uint32_t* slots, uint32_t mask, uint64_t seed);
-extern "C" __global__ void k_pk_lookup(const uint8_t* __restrict__ pks, uint32_t K, uint32_t align, const uint32_t* __restrict__ slots,
-                                       uint32_t mask, uint64_t seed, const uint32_t* __restrict__ tab_keys, const g1a* __restrict__ tab_aff,
-                                       const uint8_t* __restrict__ tab_code, g1a* __restrict__ pk_aff, uint8_t* __restrict__ pk_code,
-                                       uint32_t* __restrict__ miss, unsigned long long* __restrict__ stat);
-extern "C" __global__ void k_pk_decompress_list(const uint8_t* __restrict__ pks, const uint32_t* __restrict__ list, g1a* __restrict__ pk_aff,
-                                                uint8_t* __restrict__ pk_code);
-extern "C" __global__ void k_pk_resolve(const uint8_t* __restrict__ pks, uint32_t n, uint32_t align, const uint32_t* __restrict__ slots,
-                                        uint32_t mask, uint64_t seed, const uint32_t* __restrict__ tab_keys, uint32_t* __restrict__ idx_out);
-#define TB_PKX_BLOCK 256u
+#define TB_PKX_BLOCK 256u  // threads per workgroup of the key index's kernels (k_pkindex.hip)
 
 // The widest loads a key array at p allows (k_pkindex.hip pkx_load_key).
 inline uint32_t pkx_align(const void* p) {
@@ -347,10 +332,11 @@ int pk_lookup_reserve(dev_ctx& c, uint32_t K, hipStream_t s) {
 // The key stage of K byte keys: affine points and validity codes into pk_aff /
 // pk_code.  With a table index on the device (pk_lookup_on, pk_lookup_reserve
 // called) it is two steps: launch_pk_lookup -- k_pk_lookup copies the keys the
-// table knows and lists the others -- then launch_pk_decompress with `listed`
-// -- k_pk_decompress_list decompresses that list.  The same bytes give the
-// same point and code either way, since the table's entries came from
-// k_pk_decompress.  Without an index: k_pk_decompress over all K.
+// table knows and lists the others -- then k_pk_decompress_list decompresses
+// that list.  The same bytes give the same point and code either way, since
+// the table's entries came from k_pk_decompress.  Without an index:
+// k_pk_decompress over all K.  launch_byte_keys queues the whole stage on s;
+// looked_up: the caller has queued launch_pk_lookup already, on a stream s waits for.
 int launch_pk_lookup(dev_ctx& c, hipStream_t s, const uint8_t* pks, uint32_t K, g1a* pk_aff, uint8_t* pk_code) {
   uint32_t* miss = c.pkx_miss.as<uint32_t>();
   HIPCHK(hipMemsetAsync(miss, 0, 4, s));
@@ -359,12 +345,18 @@ int launch_pk_lookup(dev_ctx& c, hipStream_t s, const uint8_t* pks, uint32_t K, 
                      c.tab_code.as<const uint8_t>(), pk_aff, pk_code, miss, c.pkx_stat.as<unsigned long long>());
   return TBLS_SUCCESS;
 }
-void launch_pk_decompress(dev_ctx& c, hipStream_t s, const uint8_t* pks, uint32_t K, g1a* pk_aff, uint8_t* pk_code, bool listed) {
+int launch_byte_keys(dev_ctx& c, hipStream_t s, const uint8_t* pks, uint32_t K, g1a* pk_aff, uint8_t* pk_code, bool looked_up = false) {
+  if (!K) return TBLS_SUCCESS;
   const dim3 blk(TB_BLOCK), g((K + TB_BLOCK - 1) / TB_BLOCK);
-  if (listed)  // the grid covers K: the list's length is only known on the device
-    hipLaunchKernelGGL(k_pk_decompress_list, g, blk, 0, s, pks, c.pkx_miss.as<const uint32_t>(), pk_aff, pk_code);
-  else
+  if (!pk_lookup_on(c)) {
     hipLaunchKernelGGL(k_pk_decompress, g, blk, 0, s, pks, K, pk_aff, pk_code);
+    return TBLS_SUCCESS;
+  }
+  if (!looked_up)
+    if (const int rc = launch_pk_lookup(c, s, pks, K, pk_aff, pk_code)) return rc;
+  // the grid covers K: the list's length is only known on the device
+  hipLaunchKernelGGL(k_pk_decompress_list, g, blk, 0, s, pks, c.pkx_miss.as<const uint32_t>(), pk_aff, pk_code);
+  return TBLS_SUCCESS;
 }
 
 // One launch_partial call: the batch, its plan, the workspace and the streams
@@ -379,10 +371,10 @@ struct partial_run {
   const key_src& keys;
   hipStream_t s, sa, sb, sh;  // the caller's, keys, signatures + bucket sums, hash
   bool late_join;             // bp.late_join with the streams side by side
-  // Byte keys on a device with a table index (pk_lookup_on): look the keys up
-  // first.  pre_lookup: launch_partial has queued the lookup on the caller's
-  // stream ahead of the fork, and the key stream starts at the misses.
-  bool lookup, pre_lookup;
+  // Byte keys on a device with a table index (pk_lookup_on): launch_partial
+  // has queued the lookup on the caller's stream ahead of the fork, and the
+  // key stream starts at the misses.
+  bool pre_lookup;
   const uint32_t n = b.n;
   const dim3 blk = dim3(TB_BLOCK), g = dim3((b.n + TB_BLOCK - 1) / TB_BLOCK);  // one thread per set
   g1a* sig_P() const { return bp.pp.msm ? nullptr : W.P + n; }                 // -[r_i] g1 of the sets' signature pairs
@@ -440,9 +432,7 @@ struct partial_run {
       TB_EV(1, sa);
       TB_EV(2, sa);
     } else {
-      if (lookup && !pre_lookup)
-        if (const int rc = launch_pk_lookup(c, sa, b.pks, bp.n_keys, W.pk_aff, W.pk_code)) return rc;
-      if (bp.n_keys) launch_pk_decompress(c, sa, b.pks, bp.n_keys, W.pk_aff, W.pk_code, lookup);  // the keys the table does not hold, or all
+      if (const int rc = launch_byte_keys(c, sa, b.pks, bp.n_keys, W.pk_aff, W.pk_code, pre_lookup)) return rc;
       TB_EV(1, sa);
       TB_EV(2, sa);
       launch_set_pk(sa, n, bp.w2, bp.multi, b.pk_off, keys, b.rand, W.P, W.set_code, W.n_bad, W.mlist, W.mcnt, sig_P(), comb);
@@ -591,9 +581,8 @@ int launch_partial(dev_ctx& c, const tbls_dev_batch& b, hipStream_t s, void* par
   // without a table, although no stage's own time grew; ahead of the fork: 8.9,
   // 9.0, 8.8.  `serial` keeps the lookup inside the key stage's
   // bracket, for the exclusive stage times.
-  const bool lookup = bp.key == key_kind::decompress && bp.n_keys && pk_lookup_on(c);
-  const partial_run run{c, b, o, bp, W, keys, s, o.serial ? s : c.aux[0], o.serial ? s : c.aux[1], o.serial ? s : c.aux[2], late_join,
-                        lookup, lookup && !o.serial};
+  const bool pre_lookup = bp.key == key_kind::decompress && bp.n_keys && pk_lookup_on(c) && !o.serial;
+  const partial_run run{c, b, o, bp, W, keys, s, o.serial ? s : c.aux[0], o.serial ? s : c.aux[1], o.serial ? s : c.aux[2], late_join, pre_lookup};
   HIPCHK(hipMemsetAsync(W.set_code, 0, 2 * align_up(bp.pp.n_pairs), s));  // set_code and sig_code (adjacent)
   HIPCHK(hipMemsetAsync(W.n_bad, 0, 4, s));
   if (run.pre_lookup) {
@@ -673,41 +662,6 @@ dev_ctx* ctx_for(int d) {
   return g_ctx[d];
 }
 
-// ---------------------------------------------------------------------------
-// host-side packing of tbls_set arrays into one contiguous staging image
-// ---------------------------------------------------------------------------
-struct packed {
-  size_t off_pks, off_pkoff, off_msgs, off_msgoff, off_sigs, off_rand, off_dst, total;
-  uint32_t n, K, M;
-};
-
-// keys of a set: 48-byte encodings (tbls_set) or 4-byte table indices (tbls_set_idx)
-// A bitfield set inside the library: n_pks is its row in the key area, in
-// 4-byte words (the stride of every row of the call); size: the committee's
-// size the caller saw (checked again under the device lock).
-struct set_bits_i {
-  const uint8_t* bits;
-  uint32_t n_pks;
-  const uint8_t* msg;
-  uint32_t msg_len;
-  const uint8_t* sig;
-  uint32_t slot, size;
-};
-inline const void* set_keys(const tbls_set& s) { return s.pks; }
-inline const void* set_keys(const tbls_set_idx& s) { return s.key_idx; }
-template <class SET>
-constexpr size_t key_bytes() { return std::is_same<SET, tbls_set>::value ? 48 : 4; }
-
-template <class SET>
-inline void pack_keys(uint8_t* dst, const SET& s) {
-  if (s.n_pks) memcpy(dst, set_keys(s), (size_t)s.n_pks * key_bytes<SET>());
-}
-inline void pack_keys(uint8_t* dst, const set_bits_i& s) {  // the bit row, zero-padded to its stride
-  const size_t nb = (s.size + 7u) / 8u;
-  memset(dst, 0, (size_t)s.n_pks * 4);
-  memcpy(dst, s.bits, nb);
-}
-
 // The keys of sets[lo, hi) against device c's state, under its lock (a reload
 // cannot interleave): table indices below the table's size; bit rows over a
 // loaded committee of the size the caller saw.
@@ -726,51 +680,6 @@ int check_keys(const dev_ctx* c, const SET* sets, size_t lo, size_t hi) {
         return TBLS_BAD_ARGUMENT;
   }
   return TBLS_SUCCESS;
-}
-
-template <class SET>
-packed pack_layout(const SET* sets, size_t lo, size_t hi, uint32_t dlen) {
-  packed p;
-  p.n = (uint32_t)(hi - lo);
-  uint64_t K = 0, M = 0;
-  for (size_t i = lo; i < hi; i++) {
-    K += sets[i].n_pks;
-    M += sets[i].msg_len;
-  }
-  p.K = (uint32_t)K;
-  p.M = (uint32_t)M;
-  size_t o = 0;
-  p.off_pks = o;    o = align_up(o + (size_t)K * key_bytes<SET>());
-  p.off_pkoff = o;  o = align_up(o + ((size_t)p.n + 1) * 4);
-  p.off_msgs = o;   o = align_up(o + (M ? M : 1));
-  p.off_msgoff = o; o = align_up(o + ((size_t)p.n + 1) * 4);
-  p.off_sigs = o;   o = align_up(o + (size_t)p.n * 96);
-  p.off_rand = o;   o = align_up(o + (size_t)p.n * 8);
-  p.off_dst = o;    o = align_up(o + (dlen ? dlen : 1));
-  p.total = o;
-  return p;
-}
-
-template <class SET>
-void pack_fill(uint8_t* h, const packed& p, const SET* sets, size_t lo, const uint64_t* rand, const uint8_t* dst, uint32_t dlen) {
-  uint32_t* pkoff = (uint32_t*)(h + p.off_pkoff);
-  uint32_t* moff = (uint32_t*)(h + p.off_msgoff);
-  uint64_t* rr = (uint64_t*)(h + p.off_rand);
-  uint32_t k = 0, m = 0;
-  for (uint32_t i = 0; i < p.n; i++) {
-    const SET& s = sets[lo + i];
-    pkoff[i] = k;
-    moff[i] = m;
-    pack_keys(h + p.off_pks + (size_t)k * key_bytes<SET>(), s);
-    if (s.msg_len) memcpy(h + p.off_msgs + m, s.msg, s.msg_len);
-    memcpy(h + p.off_sigs + (size_t)i * 96, s.sig, 96);
-    rr[i] = rand ? rand[lo + i] : 1;
-    k += s.n_pks;
-    m += s.msg_len;
-  }
-  pkoff[p.n] = k;
-  moff[p.n] = m;
-  if (dlen) memcpy(h + p.off_dst, dst, dlen);
 }
 
 const uint8_t ETH2_DST[] = "BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_";
@@ -793,7 +702,7 @@ int shard_launch(dev_ctx* c, const SET* sets, size_t lo, size_t hi, const uint64
   hipStream_t s = c->stream;
   if (in_total > c->in.cap || in_total > c->hin.cap) HIPCHK(hipStreamSynchronize(s));  // buffers may still be read
   if (c->hin.ensure(in_total) || c->in.ensure(in_total)) return TBLS_DEVICE_ERROR;
-  pack_fill(c->hin.b(), p, sets, lo, rand, dst, dlen);
+  pack_fill(c->hin.as<uint8_t>(), p, sets, lo, rand, dst, dlen);
   HIPCHK(hipMemcpyAsync(c->in.p, c->hin.p, p.total, hipMemcpyHostToDevice, s));
   uint8_t* di = c->in.as<uint8_t>();
   tbls_dev_batch b;
@@ -824,20 +733,20 @@ int shard_codes(dev_ctx* c, const ws_layout& L, uint32_t n, uint8_t* codes_host)
   if (!n) return TBLS_SUCCESS;
   if (c->hout.ensure(2 * (size_t)n)) return TBLS_DEVICE_ERROR;
   HIPCHK(hipMemcpyAsync(c->hout.p, c->ws.as<uint8_t>(L.set_code), n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(c->hout.b() + n, c->ws.as<uint8_t>(L.sig_code), n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(c->hout.as<uint8_t>() + n, c->ws.as<uint8_t>(L.sig_code), n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   for (uint32_t i = 0; i < n; i++) {
-    const uint8_t a = c->hout.b()[i], bb = c->hout.b()[n + i];
+    const uint8_t a = c->hout.as<uint8_t>()[i], bb = c->hout.as<uint8_t>()[n + i];
     codes_host[i] = bb ? bb : a;
   }
   return TBLS_SUCCESS;
 }
 
 // One device: shard -> final exponentiation straight from the device-resident
-// partial record (no host round trip).  codes_host (nullable): per-set codes.
-template <class SET>
-int verify_on_device(int d, const SET* sets, size_t n, const uint64_t* rand, const uint8_t* dst, uint32_t dlen, int* ok,
-                     uint8_t* codes_host, double* dev_ms) {
+// partial record (no host round trip), for the calls with a DST of their own
+// or per-set codes (codes_host, nullable); batches go through batch_pass.
+int verify_on_device(int d, const tbls_set* sets, size_t n, const uint64_t* rand, const uint8_t* dst, uint32_t dlen, int* ok,
+                     uint8_t* codes_host) {
   dev_ctx* c = ctx_for(d);
   if (!c) return TBLS_DEVICE_ERROR;
   std::lock_guard<std::mutex> lk(c->mu);
@@ -848,11 +757,6 @@ int verify_on_device(int d, const SET* sets, size_t n, const uint64_t* rand, con
   if (rc) return rc;
   rc = launch_final(*c, dpart, 1, c->stream, ok);  // synchronizes c->stream
   if (rc) return rc;
-  if (dev_ms) {
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, c->e_t0, c->e_t1);
-    *dev_ms = ms;
-  }
   return codes_host ? shard_codes(c, L, nn, codes_host) : TBLS_SUCCESS;
 }
 
@@ -884,10 +788,6 @@ int verify_on_device(int d, const SET* sets, size_t n, const uint64_t* rand, con
 // settle layout (pair_plan settle: one signature pair per set, split
 // kernels), which runs the per-set stages and the line kernel only.
 // ---------------------------------------------------------------------------
-extern "C" __global__ void k_group_test_coop(const fp12* __restrict__ vals, uint32_t stride, uint32_t nseg, const uint32_t* __restrict__ list,
-                                             uint8_t* __restrict__ out);  // k_pair.hip
-extern "C" __global__ void k_settle_mask(const uint8_t* __restrict__ set_code, uint32_t n, uint8_t* __restrict__ skip);  // k_pair.hip
-
 // Group tests of the listed groups of a segmented value array on c's stream:
 // pass[k] = 1 iff group list[k] tests 1.
 static int group_tests(dev_ctx* c, const fp12* vals, uint32_t stride, uint32_t nseg, const std::vector<uint32_t>& list, uint32_t* dlist,
@@ -911,23 +811,11 @@ static int settle_sets(dev_ctx* c, const ws_layout& L, uint32_t n, uint8_t* ok) 
   std::vector<uint8_t> codes(n);
   int rc = shard_codes(c, L, n, codes.data());  // synchronizes the stream
   if (rc) return rc;
-  const uint32_t F = TB_SETTLE_FAN, nseg = settle_nseg(n);
-  const uint32_t nA = (n + F - 1) / F, nB = (nA + F - 1) / F;
-  size_t o = 0;
-  const size_t oV = o;
-  o = align_up(o + (size_t)nseg * n * sizeof(fp12));
-  const size_t oA = o;
-  o = align_up(o + (size_t)nseg * nA * sizeof(fp12));
-  const size_t oB = o;
-  o = align_up(o + (size_t)nseg * nB * sizeof(fp12));
-  const size_t oL = o;
-  o = align_up(o + (size_t)n * 4);
-  const size_t oO = o;
-  o = align_up(o + n);
-  if (c->sws.ensure(o)) return TBLS_DEVICE_ERROR;
-  uint8_t* sw = c->sws.as<uint8_t>();
+  const settle_layout S(n);
+  const uint32_t F = TB_SETTLE_FAN, nseg = S.nseg, nA = S.nA, nB = S.nB;
+  if (c->sws.ensure(S.total)) return TBLS_DEVICE_ERROR;
   uint8_t* w = c->ws.as<uint8_t>();
-  fp12 *V = (fp12*)(sw + oV), *A = (fp12*)(sw + oA), *B = (fp12*)(sw + oB);
+  fp12 *V = c->sws.as<fp12>(S.V), *A = c->sws.as<fp12>(S.A), *B = c->sws.as<fp12>(S.B);
   hipStream_t s = c->stream;
   const uint32_t g_pad = (n + TB_BLOCK - 1) / TB_BLOCK * TB_BLOCK;
   hipLaunchKernelGGL(k_settle_mask, dim3((n + 255) / 256), dim3(256), 0, s, (const uint8_t*)(w + L.set_code), n, w + L.skip);
@@ -937,8 +825,8 @@ static int settle_sets(dev_ctx* c, const ws_layout& L, uint32_t n, uint8_t* ok) 
   hipLaunchKernelGGL(k_fp12_prod_wave_seg, dim3(nA, nseg), dim3(64), 0, s, (const fp12*)V, n, n, nseg, n, F, A, nA);
   hipLaunchKernelGGL(k_fp12_prod_wave_seg, dim3(nB, nseg), dim3(64), 0, s, (const fp12*)A, nA, nA, nseg, nA, F, B, nB);
   HIPCHK(hipGetLastError());
-  uint32_t* dlist = (uint32_t*)(sw + oL);
-  uint8_t* dout = sw + oO;
+  uint32_t* dlist = c->sws.as<uint32_t>(S.list);
+  uint8_t* dout = c->sws.as<uint8_t>(S.out);
   std::vector<uint32_t> lb(nB), la, l0;
   for (uint32_t b = 0; b < nB; b++) lb[b] = b;
   std::vector<uint8_t> pb, pa, p0;
@@ -1151,6 +1039,66 @@ void for_each_shard(int G, const FN& fn) {
   for (auto& x : th) x.join();
 }
 
+// The randomized batch over sets[0, n) (n > 0, every set with keys), the one
+// pass behind tbls_batch_verify* and tbls_batch_verify_each: place the batch
+// (place_plan), lock the placed devices in ascending order, stage and launch
+// each shard (one host thread per shard when there are several), gather the
+// partial records on the lowest device unless the one record is final as it
+// lies, and run the final exponentiation there.  The locks and the placement
+// last as long as the pass, so a caller can settle from the shards'
+// workspaces (L) under them.
+template <class SET>
+struct batch_pass {
+  placed pl;  // declared first: the batch counts on its devices until the locks are gone
+  std::vector<std::unique_lock<std::mutex>> locks;
+  std::vector<ws_layout> L;  // per shard, of the pipeline that ran
+  double device_ms = 0;      // the shards' e_t0 .. e_t1, summed
+  dev_ctx* ctx(int g) const { return ctx_for(pl.dev[g]); }
+
+  int run(const SET* sets, size_t n, const uint64_t* rand, int n_gpus, int* ok) {
+    place_batch(pl, n, [&](size_t i) { return sets[i].n_pks; }, n_gpus, shard_min(), shard_knee());
+    const int G = pl.G;
+    for (int g = 0; g < G; g++) locks.emplace_back(ctx(g)->mu);  // only the placed devices, ascending: no deadlock
+    L.resize(G);
+    std::vector<uint8_t*> dpart(G, nullptr);
+    std::vector<int> rcs(G, 0);
+    for_each_shard(G, [&](int g) {
+      uint32_t nn;
+      rcs[g] = shard_launch(ctx(g), sets, pl.cut[g], pl.cut[g + 1], rand, ETH2_DST, 43, &dpart[g], L[g], &nn);
+    });
+    for (int g = 0; g < G; g++)
+      if (rcs[g]) return rcs[g];
+    dev_ctx* root = ctx(0);
+    const void* recs = dpart[0];
+    if (G > 1 || gather_forced()) {
+      if (const int rc = gather_partials(gather_sel(), pl.dev, G, dpart)) return rc;
+      recs = root->recs.p;
+    }
+    if (const int rc = launch_final(*root, recs, (uint32_t)G, root->stream, ok)) return rc;  // synchronizes the root's stream
+    // the pipelines' device times, read here: a settle re-records the events
+    // (its re-staged chunks run shard_launch again).  The root is current and idle.
+    for (int g = 0; g < G; g++) {
+      dev_ctx* c = ctx(g);
+      if (g) {
+        (void)hipSetDevice(c->dev);
+        (void)hipStreamSynchronize(c->stream);
+      }
+      float ms = 0;
+      (void)hipEventElapsedTime(&ms, c->e_t0, c->e_t1);
+      device_ms += ms;
+    }
+    return TBLS_SUCCESS;
+  }
+
+  // total_ms since t0; device_ms is the batch pass only
+  void timing(tbls_timing* t, std::chrono::steady_clock::time_point t0) const {
+    if (!t) return;
+    t->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    t->device_ms = device_ms;
+    t->n_devices = (uint32_t)pl.G;
+  }
+};
+
 // The device-resident API's way in: fn(c, s) with device `device` locked and
 // current, s the caller's stream (or the device's own) and the default DST
 // in c.dstb (uploaded on first use).
@@ -1185,6 +1133,27 @@ int with_device(const std::function<int(dev_ctx&)>& fn) {
   const int rc = fn(*c);
   (void)ws_release(*c, c->stream);
   return rc;
+}
+
+// The table and committee calls' way in: fn(c) for each device of the library
+// in turn, locked and current.  after_ws: c.stream is first ordered after the
+// workspace's last user (device-API partials queued on a caller's stream may
+// still read the table); drain: and synchronized.  Stops at the first error.
+template <class FN>
+int each_device(bool after_ws, bool drain, const FN& fn) {
+  std::vector<dev_ctx*> devs;
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    devs = g_ctx;
+  }
+  for (dev_ctx* c : devs) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->dev));
+    if (after_ws) HIPCHK(ws_acquire(*c, c->stream));
+    if (drain) HIPCHK(hipStreamSynchronize(c->stream));
+    if (const int rc = fn(c)) return rc;
+  }
+  return TBLS_SUCCESS;
 }
 
 int stage_in(dev_ctx& c, const upload& u, uint8_t** d) {
@@ -1256,25 +1225,7 @@ extern "C" int tbls_init(int n_devices, uint32_t flags) {
     count = n_devices;
   for (int d = 0; d < count; d++) {
     dev_ctx* c = new dev_ctx();
-    c->dev = d % hw;
-    int prio_lo = 0, prio_hi = 0;
-    if (hipSetDevice(c->dev) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->aux[0], hipStreamNonBlocking) != hipSuccess ||
-        hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess ||
-        hipStreamCreateWithPriority(&c->aux[1], hipStreamNonBlocking, prio_hi) != hipSuccess ||
-        hipStreamCreateWithPriority(&c->aux[2], hipStreamNonBlocking, prio_hi) != hipSuccess ||
-        hipEventCreateWithFlags(&c->e_join[2], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->e_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->e_join[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->e_join[1], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->e_sig, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->e_ws, hipEventDisableTiming) != hipSuccess || hipEventCreate(&c->e_t0) != hipSuccess ||
-        hipEventCreate(&c->e_t1) != hipSuccess || c->comb.ensure(TB_MSM_BUCKETS * sizeof(g1a))) {
-      delete c;
-      break;
-    }
-    hipLaunchKernelGGL(k_g1_comb_init, dim3(TB_MSM_BUCKETS / TB_BLOCK), dim3(TB_BLOCK), 0, c->stream, c->comb.as<g1a>());
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+    if (!c->init(d % hw)) {
       delete c;
       break;
     }
@@ -1293,32 +1244,7 @@ extern "C" void tbls_shutdown(void) {
       for (ncclComm_t cm : kv.second) (void)g_rccl.CommDestroy(cm);
   g_rccl.comms.clear();
   g_rccl.ok = g_rccl.tried = false;
-  for (dev_ctx* c : g_ctx) {
-    (void)hipSetDevice(c->dev);
-    if (c->in.p) (void)hipFree(c->in.p);
-    if (c->ws.p) (void)hipFree(c->ws.p);
-    if (c->fin.p) (void)hipFree(c->fin.p);
-    if (c->dstb.p) (void)hipFree(c->dstb.p);
-    if (c->recs.p) (void)hipFree(c->recs.p);
-    if (c->sws.p) (void)hipFree(c->sws.p);
-    if (c->comb.p) (void)hipFree(c->comb.p);
-    if (c->tab_aff.p) (void)hipFree(c->tab_aff.p);
-    if (c->tab_code.p) (void)hipFree(c->tab_code.p);
-    if (c->cmt.p) (void)hipFree(c->cmt.p);
-    for (dbuf* b : {&c->tab_keys, &c->pkx_slots, &c->pkx_stat, &c->pkx_miss}) b->release();
-    if (c->hin.p) (void)hipHostFree(c->hin.p);
-    if (c->hout.p) (void)hipHostFree(c->hout.p);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    for (int i = 0; i < 3; i++)
-      if (c->aux[i]) (void)hipStreamDestroy(c->aux[i]);
-    if (c->e_fork) (void)hipEventDestroy(c->e_fork);
-    if (c->e_sig) (void)hipEventDestroy(c->e_sig);
-    for (hipEvent_t e : {c->e_ws, c->e_t0, c->e_t1})
-      if (e) (void)hipEventDestroy(e);
-    for (int i = 0; i < 3; i++)
-      if (c->e_join[i]) (void)hipEventDestroy(c->e_join[i]);
-    delete c;
-  }
+  for (dev_ctx* c : g_ctx) delete c;
   g_ctx.clear();
   g_inited = false;
 }
@@ -1337,45 +1263,10 @@ int batch_verify_impl(const SET* sets, size_t n, const uint64_t* rand, int n_gpu
   if (n == 0) return TBLS_SUCCESS;  // BLS.java:240-241
   for (size_t i = 0; i < n; i++)
     if (sets[i].n_pks == 0) return TBLS_BAD_ARGUMENT;
-  placed pl;  // the devices and shard cuts (place_plan), counted as busy until we return
-  place_batch(pl, n, [&](size_t i) { return sets[i].n_pks; }, n_gpus, shard_min(), shard_knee());
-  const int G = pl.G;
-  std::vector<double> dms(G, 0);
-  int rc = TBLS_SUCCESS;
-  if (G == 1 && !gather_forced()) {
-    rc = verify_on_device(pl.dev[0], sets, n, rand, ETH2_DST, 43, ok, nullptr, &dms[0]);
-  } else {
-    // only the placed devices' locks, for the whole batch, in ascending device order (no deadlock)
-    std::vector<std::unique_lock<std::mutex>> locks;
-    for (int g = 0; g < G; g++) locks.emplace_back(ctx_for(pl.dev[g])->mu);
-    std::vector<uint8_t*> dpart(G, nullptr);
-    std::vector<int> rcs(G, 0);
-    for_each_shard(G, [&](int g) {
-      ws_layout L;
-      uint32_t nn;
-      rcs[g] = shard_launch(ctx_for(pl.dev[g]), sets, pl.cut[g], pl.cut[g + 1], rand, ETH2_DST, 43, &dpart[g], L, &nn);
-    });
-    for (int g = 0; g < G; g++)
-      if (rcs[g]) return rcs[g];
-    rc = gather_partials(gather_sel(), pl.dev, G, dpart);
-    dev_ctx* root = ctx_for(pl.dev[0]);
-    if (!rc) rc = launch_final(*root, root->recs.p, (uint32_t)G, root->stream, ok);
-    for (int g = 0; g < G && !rc; g++) {
-      dev_ctx* c = ctx_for(pl.dev[g]);
-      (void)hipSetDevice(c->dev);
-      (void)hipStreamSynchronize(c->stream);
-      float ms = 0;
-      (void)hipEventElapsedTime(&ms, c->e_t0, c->e_t1);
-      dms[g] = ms;
-    }
-  }
-  if (t) {
-    t->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    t->device_ms = 0;
-    for (double d : dms) t->device_ms += d;
-    t->n_devices = (uint32_t)G;
-  }
-  return rc;
+  batch_pass<SET> pass;
+  if (const int rc = pass.run(sets, n, rand, n_gpus, ok)) return rc;
+  pass.timing(t, t0);
+  return TBLS_SUCCESS;
 }
 
 extern "C" int tbls_batch_verify(const tbls_set* sets, size_t n, const uint64_t* rand, int n_gpus, int* ok, tbls_timing* t) {
@@ -1384,7 +1275,8 @@ extern "C" int tbls_batch_verify(const tbls_set* sets, size_t n, const uint64_t*
 
 // tbls_batch_verify_each: the randomized batch, and on failure each set's
 // verdict settled from the batch's own work on the devices that ran it
-// (settle_range).  Sets with no keys are false and left out of the batch.
+// (settle_range), under the pass's locks.  Sets with no keys are false and
+// left out of the batch.
 extern "C" int tbls_batch_verify_each(const tbls_set* sets_in, size_t n_in, const uint64_t* rand_in, int n_gpus, int* ok, int* ok_per_set,
                                       tbls_timing* t) {
   auto t0 = std::chrono::steady_clock::now();
@@ -1406,60 +1298,26 @@ extern "C" int tbls_batch_verify_each(const tbls_set* sets_in, size_t n_in, cons
   }
   const size_t n = sets.size();
   if (n == 0) return TBLS_SUCCESS;
-  placed pl;
-  place_batch(pl, n, [&](size_t i) { return sets[i].n_pks; }, n_gpus, shard_min(), shard_knee());
-  const int G = pl.G;
-  std::vector<std::unique_lock<std::mutex>> locks;  // ascending device order: no deadlock
-  for (int g = 0; g < G; g++) locks.emplace_back(ctx_for(pl.dev[g])->mu);
-  std::vector<uint8_t*> dpart(G, nullptr);
-  std::vector<ws_layout> Ls(G);
-  std::vector<int> rcs(G, 0);
-  for_each_shard(G, [&](int g) {
-    uint32_t nn;
-    rcs[g] = shard_launch(ctx_for(pl.dev[g]), sets.data(), pl.cut[g], pl.cut[g + 1], rand.data(), ETH2_DST, 43, &dpart[g], Ls[g], &nn);
-  });
-  for (int g = 0; g < G; g++)
-    if (rcs[g]) return rcs[g];
-  int rc = TBLS_SUCCESS;
-  dev_ctx* root = ctx_for(pl.dev[0]);
-  if (G == 1 && !gather_forced()) {
-    rc = launch_final(*root, dpart[0], 1, root->stream, ok);
-  } else {
-    rc = gather_partials(gather_sel(), pl.dev, G, dpart);
-    if (!rc) rc = launch_final(*root, root->recs.p, (uint32_t)G, root->stream, ok);
-  }
-  if (rc) return rc;
-  // the batch pipeline's device time, read before any settle re-records the
-  // shards' events (re-staged settle chunks run shard_launch again)
-  double batch_dev_ms = 0;
-  for (int g = 0; g < G; g++) {
-    dev_ctx* c = ctx_for(pl.dev[g]);
-    float ms = 0;
-    (void)hipSetDevice(c->dev);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipEventElapsedTime(&ms, c->e_t0, c->e_t1);
-    batch_dev_ms += ms;
-  }
+  batch_pass<tbls_set> pass;
+  if (const int rc = pass.run(sets.data(), n, rand.data(), n_gpus, ok)) return rc;
   std::vector<uint8_t> verdict(n, 1);
   if (!*ok) {
-    for_each_shard(G, [&](int g) {
-      dev_ctx* c = ctx_for(pl.dev[g]);
+    const placed& pl = pass.pl;
+    std::vector<int> rcs(pl.G, 0);
+    for_each_shard(pl.G, [&](int g) {
+      dev_ctx* c = pass.ctx(g);
       if (hipSetDevice(c->dev) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
         rcs[g] = TBLS_DEVICE_ERROR;
         return;
       }
-      rcs[g] = settle_range(c, sets.data(), pl.cut[g], pl.cut[g + 1], rand.data(), true, Ls[g], verdict.data() + pl.cut[g]);
+      rcs[g] = settle_range(c, sets.data(), pl.cut[g], pl.cut[g + 1], rand.data(), true, pass.L[g], verdict.data() + pl.cut[g]);
     });
-    for (int g = 0; g < G; g++)
+    for (int g = 0; g < pl.G; g++)
       if (rcs[g]) return rcs[g];
   }
   for (size_t k = 0; k < n; k++) ok_per_set[pos[k]] = verdict[k];
   if (n != n_in) *ok = 0;  // a set without keys fails the whole batch as well
-  if (t) {
-    t->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    t->device_ms = batch_dev_ms;  // the batch pass only; settling is in total_ms
-    t->n_devices = (uint32_t)G;
-  }
+  pass.timing(t, t0);       // settling is in total_ms
   return TBLS_SUCCESS;
 }
 
@@ -1470,23 +1328,14 @@ extern "C" int tbls_pk_table_load(const uint8_t* pks, size_t K, uint8_t* codes) 
   const caller_device keep;
   if (ensure_init()) return TBLS_DEVICE_ERROR;
   if (K == 0 || K > 0xffffffffu / 96) return TBLS_BAD_ARGUMENT;
-  std::vector<dev_ctx*> devs;
-  bool index;
-  {
+  const bool index = [] {
     std::lock_guard<std::mutex> lk(g_mu);
-    devs = g_ctx;
-    index = g_pk_lookup;
-  }
+    return g_pk_lookup;
+  }();
   uint64_t seed = 0;  // of this load's index: from the OS entropy source, as the randomizers
   if (index && fill_random(&seed, 1)) return TBLS_DEVICE_ERROR;
   const uint32_t cap = tb::pkx_capacity((uint32_t)K);
-  for (size_t d = 0; d < devs.size(); d++) {
-    dev_ctx* c = devs[d];
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->dev));
-    // device-API partials queued on a caller's stream may still read the old table
-    HIPCHK(ws_acquire(*c, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+  return each_device(true, true, [&](dev_ctx* c) -> int {  // the old table's last readers have finished
     c->tab_n = 0;
     c->pkx_cap = 0;                          // and no index until this load's is complete
     for (uint32_t& sz : c->cm_size) sz = 0;  // the committees' indices meant the old table
@@ -1495,7 +1344,8 @@ extern "C" int tbls_pk_table_load(const uint8_t* pks, size_t K, uint8_t* codes) 
     hipLaunchKernelGGL(k_pk_decompress, dim3((uint32_t)((K + TB_BLOCK - 1) / TB_BLOCK)), dim3(TB_BLOCK), 0, c->stream,
                        c->in.as<const uint8_t>(), (uint32_t)K, c->tab_aff.as<g1a>(), c->tab_code.as<uint8_t>());
     HIPCHK(hipGetLastError());
-    if (d == 0 && codes) HIPCHK(hipMemcpyAsync(codes, c->tab_code.p, K, hipMemcpyDeviceToHost, c->stream));
+    if (codes) HIPCHK(hipMemcpyAsync(codes, c->tab_code.p, K, hipMemcpyDeviceToHost, c->stream));
+    codes = nullptr;  // from the first device only
     if (index) {
       // the keys stay resident beside their points, and every slot is cleared:
       // nothing of an earlier table's index survives.  The stream is
@@ -1514,31 +1364,22 @@ extern "C" int tbls_pk_table_load(const uint8_t* pks, size_t K, uint8_t* codes) 
       c->pkx_seed = seed;
       c->pkx_cap = cap;
     }
-  }
-  return TBLS_SUCCESS;
+    return TBLS_SUCCESS;
+  });
 }
 
 // Drop the table, its index and the committees on every device.
 extern "C" int tbls_pk_table_clear(void) {
   const caller_device keep;
   if (ensure_init()) return TBLS_DEVICE_ERROR;
-  std::vector<dev_ctx*> devs;
-  {
-    std::lock_guard<std::mutex> lk(g_mu);
-    devs = g_ctx;
-  }
-  for (dev_ctx* c : devs) {
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->dev));
-    HIPCHK(ws_acquire(*c, c->stream));  // device-API partials on a caller's stream may still read the table
-    HIPCHK(hipStreamSynchronize(c->stream));
+  return each_device(true, true, [&](dev_ctx* c) -> int {
     c->tab_n = 0;
     c->pkx_cap = 0;
     for (uint32_t& sz : c->cm_size) sz = 0;
     for (dbuf* b : {&c->tab_aff, &c->tab_code, &c->tab_keys, &c->pkx_slots, &c->cmt}) b->release();
     if (c->pkx_stat.p) HIPCHK(hipMemset(c->pkx_stat.p, 0, 16));
-  }
-  return TBLS_SUCCESS;
+    return TBLS_SUCCESS;
+  });
 }
 
 // One device pass over n keys: the table index of each key's bytes.
@@ -1564,24 +1405,16 @@ extern "C" int tbls_pk_lookup_stats(uint64_t out[2], int reset) {
   if (!out) return TBLS_BAD_ARGUMENT;
   out[0] = out[1] = 0;
   if (ensure_init()) return TBLS_DEVICE_ERROR;
-  std::vector<dev_ctx*> devs;
-  {
-    std::lock_guard<std::mutex> lk(g_mu);
-    devs = g_ctx;
-  }
-  for (dev_ctx* c : devs) {
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->pkx_stat.p) continue;
-    HIPCHK(hipSetDevice(c->dev));
-    HIPCHK(ws_acquire(*c, c->stream));  // key stages queued on a caller's stream count too
+  return each_device(true, false, [&](dev_ctx* c) -> int {  // key stages queued on a caller's stream count too
+    if (!c->pkx_stat.p) return TBLS_SUCCESS;
     uint64_t v[2] = {0, 0};
     HIPCHK(hipMemcpyAsync(v, c->pkx_stat.p, 16, hipMemcpyDeviceToHost, c->stream));
     if (reset) HIPCHK(hipMemsetAsync(c->pkx_stat.p, 0, 16, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     out[0] += v[0];
     out[1] += v[1];
-  }
-  return TBLS_SUCCESS;
+    return TBLS_SUCCESS;
+  });
 }
 
 extern "C" size_t tbls_pk_table_size(void) {
@@ -1608,7 +1441,7 @@ static int verify_one(const uint8_t* pks, uint32_t n_pks, const uint8_t* msg, si
   uint64_t one = 1;
   placed pl;
   place_one(pl);
-  int rc = verify_on_device(pl.dev[0], &s, 1, &one, dst, (uint32_t)dlen, ok, &code, nullptr);
+  int rc = verify_on_device(pl.dev[0], &s, 1, &one, dst, (uint32_t)dlen, ok, &code);
   if (code_out) *code_out = code;
   return rc;
 }
@@ -1637,7 +1470,7 @@ static int run_each(int d, const SET* sets, size_t lo, size_t hi, uint8_t* ok_ho
   if (const int rc = check_keys(c, sets, lo, hi)) return rc;
   packed p = pack_layout(sets, lo, hi, 43);
   if (c->hin.ensure(p.total + 256) || c->in.ensure(p.total + 256)) return TBLS_DEVICE_ERROR;
-  pack_fill(c->hin.b(), p, sets, lo, nullptr, ETH2_DST, 43);  // r = 1 for every set
+  pack_fill(c->hin.as<uint8_t>(), p, sets, lo, nullptr, ETH2_DST, 43);  // r = 1 for every set
   hipStream_t s = c->stream;
   HIPCHK(ws_acquire(*c, s));
   HIPCHK(hipStreamSynchronize(s));  // ws may be reallocated below
@@ -1657,12 +1490,8 @@ static int run_each(int d, const SET* sets, size_t lo, size_t hi, uint8_t* ok_ho
   const dim3 blk(TB_BLOCK), g((n + TB_BLOCK - 1) / TB_BLOCK);
   HIPCHK(hipMemsetAsync(n_bad, 0, 4, s));
   HIPCHK(hipMemsetAsync(set_code, 0, n, s));  // k_set_pk writes failures only
-  if (K) {  // byte keys: from the table's index where it holds them, the others (or all) decompressed
-    const bool lookup = pk_lookup_on(*c);
-    if (lookup)
-      if (const int rc = launch_pk_lookup(*c, s, di + p.off_pks, K, (g1a*)(w + E.pk_aff), w + E.pk_code)) return rc;
-    launch_pk_decompress(*c, s, di + p.off_pks, K, (g1a*)(w + E.pk_aff), w + E.pk_code, lookup);
-  }
+  // byte keys: from the table's index where it holds them, the others (or all) decompressed
+  if (const int rc = launch_byte_keys(*c, s, di + p.off_pks, K, (g1a*)(w + E.pk_aff), w + E.pk_code)) return rc;
   if constexpr (bits_mode) {
     if (n) launch_set_pk_bits(s, n, keys, committee_src(*c, sets[lo].slot), rand, P, set_code, n_bad, nullptr, nullptr, 1u);
   } else {
@@ -1767,19 +1596,11 @@ extern "C" int tbls_committee_load(uint32_t slot, const uint32_t* key_idx, uint3
   const caller_device keep;
   if (ensure_init()) return TBLS_DEVICE_ERROR;
   if (slot >= TBLS_COMMITTEE_SLOTS || !key_idx || size == 0 || size > TBLS_COMMITTEE_MAX) return TBLS_BAD_ARGUMENT;
-  std::vector<dev_ctx*> devs;
-  {
-    std::lock_guard<std::mutex> lk(g_mu);
-    devs = g_ctx;
-  }
-  for (dev_ctx* c : devs) {
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->dev));
+  return each_device(false, true, [&](dev_ctx* c) -> int {
     if (!c->tab_n) return TBLS_BAD_ARGUMENT;
     for (uint32_t i = 0; i < size; i++)
       if (key_idx[i] >= c->tab_n) return TBLS_BAD_ARGUMENT;
     hipStream_t s = c->stream;
-    HIPCHK(hipStreamSynchronize(s));
     c->cm_size[slot] = 0;
     if (c->cmt.ensure((size_t)TBLS_COMMITTEE_SLOTS * TB_CM_STRIDE)) return TBLS_DEVICE_ERROR;
     uint8_t* m = c->cmt.as<uint8_t>((size_t)slot * TB_CM_STRIDE);
@@ -1799,8 +1620,8 @@ extern "C" int tbls_committee_load(uint32_t slot, const uint32_t* key_idx, uint3
     HIPCHK(hipStreamSynchronize(s));
     c->cm_sum_ok[slot] = code == TB_SUCCESS ? 1u : 0u;
     c->cm_size[slot] = size;
-  }
-  return TBLS_SUCCESS;
+    return TBLS_SUCCESS;
+  });
 }
 
 extern "C" uint32_t tbls_committee_size(uint32_t slot) {
@@ -1852,7 +1673,7 @@ extern "C" int tbls_aggregate_verify(const uint8_t* pks, const uint8_t* const* m
   for (size_t i = 0; i < n; i++) sets[i] = {pks + 48 * i, 1, msgs[i], msg_lens[i], i == 0 ? sig : INF_SIG};
   placed pl;
   place_one(pl);
-  return verify_on_device(pl.dev[0], sets.data(), n, ones.data(), ETH2_DST, 43, ok, nullptr, nullptr);
+  return verify_on_device(pl.dev[0], sets.data(), n, ones.data(), ETH2_DST, 43, ok, nullptr);
 }
 
 extern "C" int tbls_pk_validate(const uint8_t pk[48]) {

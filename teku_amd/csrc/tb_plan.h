@@ -552,5 +552,27 @@ struct each_layout {
   }
 };
 
+// scratch of settling n sets (tb_lib.hip settle_sets; byte offsets into
+// dev_ctx::sws): nseg segment rows of the n per-set Miller values, of their
+// nA group products (TB_SETTLE_FAN sets each) and of the nB products of those
+// groups; then the list of groups to test (at most n words) and the tests'
+// verdicts (a byte each)
+struct settle_layout {
+  uint32_t nseg, nA, nB;
+  size_t V, A, B, list, out, total;
+  explicit settle_layout(uint32_t n) {
+    nseg = settle_nseg(n);
+    nA = (n + TB_SETTLE_FAN - 1) / TB_SETTLE_FAN;
+    nB = (nA + TB_SETTLE_FAN - 1) / TB_SETTLE_FAN;
+    size_t o = 0;
+    V = o;    o = align_up(o + (size_t)nseg * n * sizeof(fp12));
+    A = o;    o = align_up(o + (size_t)nseg * nA * sizeof(fp12));
+    B = o;    o = align_up(o + (size_t)nseg * nB * sizeof(fp12));
+    list = o; o = align_up(o + (size_t)n * 4);
+    out = o;  o = align_up(o + n);
+    total = o;
+  }
+};
+
 }  // namespace plan
 }  // namespace tb

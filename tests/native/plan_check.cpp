@@ -4,7 +4,8 @@
 //                      and the workspace size, under the process environment
 //                      (compared with tests/golden/batch_plan.txt)
 //   plan_check check   the plan's invariants at the same sizes under the
-//                      default settings and the overrides the GPU tests use
+//                      default settings and the overrides the GPU tests use,
+//                      and the settle scratch layout's up to TB_SETTLE_MAX sets
 #include <cstring>
 #include <string>
 
@@ -146,6 +147,27 @@ static void check(uint32_t n, const source& s, bool settle, const batch_plan& bp
   }
 }
 
+// The settle scratch (settle_layout) at n sets: regions 256-byte aligned, in
+// order (each ends where the next begins, so disjoint), each large enough for
+// nseg rows of its count of Fp12 values, or n words / n bytes.
+static void check_settle(uint32_t n) {
+  g_where = "settle_layout n=" + std::to_string(n);
+  const settle_layout S(n);
+  const size_t off[] = {S.V, S.A, S.B, S.list, S.out, S.total};
+  CHECK(off[0] == 0);
+  for (size_t o : off) CHECK(o % 256 == 0);
+  for (int i = 0; i + 1 < 6; i++) CHECK(off[i] <= off[i + 1]);
+  CHECK(S.nseg == settle_nseg(n) && S.nseg >= 1 && S.nseg <= 16);
+  CHECK((uint64_t)S.nA * TB_SETTLE_FAN >= n && (uint64_t)S.nB * TB_SETTLE_FAN >= S.nA);  // every set in a group, every group in one above
+  CHECK((n == 0 || ((uint64_t)S.nA - 1) * TB_SETTLE_FAN < n) && (S.nA == 0 || ((uint64_t)S.nB - 1) * TB_SETTLE_FAN < S.nA));
+  CHECK(S.A - S.V >= (size_t)S.nseg * n * sizeof(tb::fp12));
+  CHECK(S.B - S.A >= (size_t)S.nseg * S.nA * sizeof(tb::fp12));
+  CHECK(S.list - S.B >= (size_t)S.nseg * S.nB * sizeof(tb::fp12));
+  CHECK(S.out - S.list >= (size_t)n * 4);  // a test list is at most the n sets (nA, nB <= n)
+  CHECK(S.total - S.out >= n);
+  CHECK(S.nA <= n && S.nB <= std::max(n, 1u));
+}
+
 int main(int argc, char** argv) {
   if (argc == 2 && !strcmp(argv[1], "dump")) {
     sweep(plan_env::get(), dump);
@@ -183,6 +205,8 @@ int main(int argc, char** argv) {
         check(n, s, settle, bp, ne.name.c_str());
         plans++;
       });
+    for (uint32_t n : SIZES)
+      if (n <= TB_SETTLE_MAX) check_settle(n);
     printf("plans %u failures %d\n", plans, g_fail);
     return g_fail ? 1 : 0;
   }

@@ -3,8 +3,12 @@ sanitizers"; VERDICT r1 hygiene): the host build of the kernel arithmetic
 (tb_*.h) and the C oracle, linked into tests/native/sanitize_main.cpp, built
 and run under AddressSanitizer + UndefinedBehaviorSanitizer, and the oracle's
 pthreaded batch verification under ThreadSanitizer.  GPU sanitizers are not
-available on this pool; the product library's host code (tb_lib.hip) runs
-under the -m gpu tests only."""
+available on this pool.  Of the product library's host code, the host-only
+headers have CPU checks under the same two sanitizers -- the batch plan and
+the workspace, per-set and settle layouts (tb_plan.h: test_batch_plan.py), the
+staging image of a host batch (tb_pack.h: test_pack.py) and the key index
+(tb_pkindex.h: test_pkindex.py); what stays in tb_lib.hip (contexts, launches,
+the batch pass, settling, the table calls) runs under the -m gpu tests only."""
 
 import os
 import subprocess
