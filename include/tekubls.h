@@ -346,6 +346,59 @@ int tbls_dev_batch_stage_profile(int device, const tbls_dev_batch* b, void* stre
  * wave Miller loops for small batches).  Always TBLS_SUCCESS. */
 int tbls_acc_plan(uint32_t n, uint32_t* per, uint32_t* nseg, int* split);
 
+/* ---- Grouped batches: one hash_to_G2 and one pairing per distinct message ----
+ * Attestations of one slot sign the same AttestationData, so a service batch
+ * (AggregatingSignatureVerificationService.java:187-227) carries few distinct
+ * signing roots.  The batch equation of BLS.batchVerify (BLS.java:275-336)
+ * collapses over sets that share a message,
+ *   prod_i e(r_i apk_i, H(m_i)) = prod_g e(sum_{i in g} r_i apk_i, H(m_g)),
+ * an equality in GT: the verdict is exactly the ungrouped one for the same
+ * randomizers.  With m distinct messages the pass runs m hashes and m + 64
+ * Miller loops (the signature side is always the 64-pair bucket sum). */
+enum { TBLS_GROUP_FORCE = 1u };
+
+/* tbls_batch_verify over message groups (BLS.java:275-336,
+ * AggregatingSignatureVerificationService.java:187-227): *ok and the return
+ * code equal tbls_batch_verify's on the same arguments (n = 0, empty key
+ * lists, decode failures included).  Messages are grouped by length and
+ * bytes, per device shard.  A shard of n sets with m distinct messages runs
+ * the grouped pass when grouping pays (tbls_group_plan), and with
+ * TBLS_GROUP_FORCE in flags whenever m < n; otherwise, and always when m == n,
+ * it runs tbls_batch_verify's pass. */
+int tbls_batch_verify_grouped(const tbls_set* sets, size_t n, const uint64_t* rand, int n_gpus, uint32_t flags, int* ok, tbls_timing* t);
+
+/* tbls_batch_verify_idx over message groups (BLS.java:275-336,
+ * AggregatingSignatureVerificationService.java:187-227): verdict and return
+ * code equal tbls_batch_verify_idx's (an index past the table ->
+ * TBLS_BAD_ARGUMENT). */
+int tbls_batch_verify_idx_grouped(const tbls_set_idx* sets, size_t n, const uint64_t* rand, int n_gpus, uint32_t flags, int* ok,
+                                  tbls_timing* t);
+
+/* tbls_dev_batch_partial (key_idx NULL) or tbls_dev_batch_partial_idx over
+ * message groups, always grouped (BLS.java:275-336,
+ * AggregatingSignatureVerificationService.java:187-227).  b->msgs and
+ * b->msg_off (n_msgs + 1 offsets) hold the n_msgs distinct messages; grp_off
+ * (n_msgs + 1 words) and grp_sets (b->n words), device memory, list each
+ * message's sets: message g is signed by sets grp_sets[grp_off[g] ..
+ * grp_off[g + 1]).  Every set appears in exactly one list.  The record is the
+ * one tbls_dev_batch_partial writes: its product has the same final
+ * exponentiation and its invalid-set count is the same.  Needs
+ * 0 < n_msgs < b->n (every message distinct: tbls_dev_batch_partial), else
+ * TBLS_BAD_ARGUMENT. */
+int tbls_dev_batch_partial_grouped(int device, const tbls_dev_batch* b, const uint32_t* key_idx, uint32_t n_msgs, const uint32_t* grp_off,
+                                   const uint32_t* grp_sets, void* stream, void* partial_out);
+
+/* What the grouped host entries do with a shard of n sets and n_msgs distinct
+ * messages (BLS.java:275-336, AggregatingSignatureVerificationService.java:
+ * 187-227; introspection, no device work).  *grouped: 0 the ungrouped pass
+ * whatever the flags (n_msgs == 0 or n_msgs >= n); 1 the grouped pass under
+ * TBLS_GROUP_FORCE only; 2 the grouped pass without the flag as well
+ * (n >= group_min and 100 n_msgs <= percent n; TBLS_GROUP_MIN="min[,percent]"
+ * in the environment overrides the built-in thresholds).  *n_pairs: the
+ * Miller loops of the grouped pass (n_msgs + 64) when *grouped is not 0, else
+ * of the ungrouped pass.  Always TBLS_SUCCESS. */
+int tbls_group_plan(uint32_t n, uint32_t n_msgs, int* grouped, uint32_t* n_pairs);
+
 /* Device placement of a batch (introspection for tests and tuning; no device
  * work), the function tbls_batch_verify / tbls_verify_each / the single-call
  * entries use (tb_lib.hip place_plan): n sets (n_pks[i] keys

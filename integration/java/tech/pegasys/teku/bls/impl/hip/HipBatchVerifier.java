@@ -33,6 +33,20 @@ public final class HipBatchVerifier {
    */
   public static boolean batchVerifyEach(final List<List<BLSPublicKey>> keys, final List<Bytes> messages,
                                         final List<BLSSignature> signatures, final int nGpus, final boolean[] okPerSet) {
+    return batchVerifyEach(keys, messages, signatures, nGpus, okPerSet, false);
+  }
+
+  /*
+   * The same with groupMessages: the batch first runs through
+   * tbls_batch_verify_grouped -- one hash and one pairing per distinct message
+   * where the library finds that grouping pays, the verdict of the ungrouped
+   * batch (attestations of one slot sign the same AttestationData).  A batch
+   * that passes is done; one that fails goes on to tbls_batch_verify_each,
+   * which gives the per-set verdicts as without the flag.
+   */
+  public static boolean batchVerifyEach(final List<List<BLSPublicKey>> keys, final List<Bytes> messages,
+                                        final List<BLSSignature> signatures, final int nGpus, final boolean[] okPerSet,
+                                        final boolean groupMessages) {
     final int n = keys.size();
     if (messages.size() != n || signatures.size() != n || okPerSet.length < n) {
       throw new IllegalArgumentException("Different collection sizes");
@@ -63,6 +77,13 @@ public final class HipBatchVerifier {
       rand[i] = HipBLS12381.nextBatchRandomMultiplier();
     }
     final int[] ok = new int[1];
+    if (groupMessages) {
+      final int rcGrouped = TekuBlsHipGrouped.batchVerifyGrouped(pks, nPks, msgs, msgOff, sigs, rand, nGpus, 0, ok);
+      if (rcGrouped == TekuBlsHip.SUCCESS && ok[0] == 1) {
+        java.util.Arrays.fill(okPerSet, 0, n, true);
+        return true;
+      } // a failed batch, an empty key list or an error: the per-set call decides
+    }
     final int[] each = new int[n];
     final int rc = TekuBlsHip.batchVerifyEach(pks, nPks, msgs, msgOff, sigs, rand, nGpus, ok, each);
     if (rc != TekuBlsHip.SUCCESS) {

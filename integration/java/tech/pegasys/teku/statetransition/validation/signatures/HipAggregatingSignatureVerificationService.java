@@ -17,6 +17,10 @@
  *     devices; a batch that drains the queue may shard over every idle
  *     device (tb_lib.hip place_plan: down to 4,096 sets per device on an
  *     idle node).
+ *  4. groupMessages (opt-in, off by default): the batch first runs over message
+ *     groups (tbls_batch_verify_grouped: one hash and one pairing per distinct
+ *     message where grouping pays, the same verdict); only a batch that fails
+ *     goes on to tbls_batch_verify_each.
  * Python mirror and tests: teku_amd/service.py, tests/test_service.py
  * (placement simulated over 8 devices), tests/test_gpu_configs.py.
  */
@@ -53,6 +57,7 @@ public class HipAggregatingSignatureVerificationService extends SignatureVerific
   private final AsyncRunner completionRunner;
   private final int numThreads;
   private final int maxBatchSize;
+  private final boolean groupMessages;
   private final BlockingQueue<Task> queue;
   private final AsyncRunner asyncRunner;
   private final Counter batchCounter;
@@ -65,6 +70,17 @@ public class HipAggregatingSignatureVerificationService extends SignatureVerific
       final AsyncRunner completionRunner,
       final int queueCapacity,
       final int maxBatchSize) {
+    this(metricsSystem, asyncRunnerFactory, completionRunner, queueCapacity, maxBatchSize, false);
+  }
+
+  public HipAggregatingSignatureVerificationService(
+      final MetricsSystem metricsSystem,
+      final AsyncRunnerFactory asyncRunnerFactory,
+      final AsyncRunner completionRunner,
+      final int queueCapacity,
+      final int maxBatchSize,
+      final boolean groupMessages) {
+    this.groupMessages = groupMessages;
     this.numThreads = HipBatchVerifier.deviceCount();
     this.asyncRunner = asyncRunnerFactory.create(getClass().getSimpleName(), numThreads);
     this.completionRunner = completionRunner;
@@ -168,7 +184,8 @@ public class HipAggregatingSignatureVerificationService extends SignatureVerific
     try {
       batchIsValid =
           allKeys.isEmpty()
-              || HipBatchVerifier.batchVerifyEach(allKeys, allMessages, allSignatures, nGpus, okPerSet);
+              || HipBatchVerifier.batchVerifyEach(
+                  allKeys, allMessages, allSignatures, nGpus, okPerSet, groupMessages);
     } catch (RuntimeException e) {
       for (Task task : tasks) {
         task.result.completeExceptionally(e);

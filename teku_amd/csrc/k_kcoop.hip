@@ -13,6 +13,9 @@
 //   k_sig_check_coop  4 sets per 64-thread wave: decode, Fp2 square root (two
 //                     coop exponentiations), G2 subgroup check; the outputs of
 //                     k_sig_check in skip mode 1.
+// Further down: the multi-key aggregation (k_set_pk_agg_coop), the
+// sync-committee bit rows (k_set_pk_bits_coop) and the per-group sums of
+// grouped batches (k_group_items, k_group_pk_sum_coop) on the same 32-row layout.
 #include "tb_kdecl.h"
 #include "tb_comb.h"
 #include "tb_ccurve.h"
@@ -722,5 +725,179 @@ extern "C" __global__ void __launch_bounds__(KA_ROWS * 16)
       return kb_set_generic(row, members, size, tab_aff, tab_code, tab_n, r, o);
     });
     __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Grouped batches (tb_group.h, DESIGN.md "Grouped batches"): the sets that
+// sign one message share one main pair (sum_{i in g} [r_i] apk_i, H(m_g)).
+// The key stage leaves the sets' [r_i] apk_i in a per-set array; these kernels
+// sum them per group, over the CSR (grp_off, grp_sets), in the layout of
+// k_set_pk_agg_coop: one 512-thread workgroup per sum, row q walks members q,
+// q + 32, ... with coop mixed additions, the 32 row sums meet in the LDS row
+// tree (ka_tree) and lane 0 of row 0 inverts once (ka_affine).
+//   * Members whose code is nonzero (an invalid set: its point is undefined)
+//     are left out; the set already counts in n_bad, which decides the verdict.
+//   * The coop additions have no exceptional-case branches, and here P == +-Q
+//     is ordinary input (one key twice under one message with equal
+//     randomizers; a key and its negation): such a sum ends with Z = 0, and
+//     lane 0 then sums the members again with the exact formulas
+//     (gs_exact).  A sum that is truly infinity, or has no member left, gets
+//     its flag set: e(inf, H) = 1, the pair is skipped and nothing has failed.
+//   * A sum of one member is a copy: no tree, no inversion.
+//   * A group of more than `walk` members (tb_plan.h group_walk) is split
+//     into items of `walk` members: k_group_items numbers the items
+//     (item_first[g]: group g's first), pass 0 writes the items' sums to
+//     part / part_skip (straight to PG / pskip for a group of one item) and
+//     pass 1 sums the items of every split group the same way.
+// Offsets and indices come from the caller of the device entry: they are
+// clamped to the arrays (n members, items_max items), never trusted.
+// ---------------------------------------------------------------------------
+extern "C" __global__ void __launch_bounds__(256)
+    k_group_items(const uint32_t* __restrict__ grp_off, uint32_t m, uint32_t n, uint32_t walk, uint32_t* __restrict__ item_first) {
+  __shared__ uint32_t part[256];
+  const uint32_t t = threadIdx.x, per = (m + 255u) / 256u, lo = std::min(m, t * per), hi = std::min(m, lo + per);
+  const auto items = [&](uint32_t g) {
+    const uint32_t e = std::min(grp_off[g + 1], n), b = std::min(grp_off[g], e), c = e - b;
+    return c ? (c + walk - 1u) / walk : 1u;
+  };
+  uint32_t sum = 0;
+  for (uint32_t g = lo; g < hi; g++) sum += items(g);
+  part[t] = sum;
+  __syncthreads();
+  uint32_t base = 0;
+  for (uint32_t k = 0; k < t; k++) base += part[k];
+  for (uint32_t g = lo; g < hi; g++) {
+    item_first[g] = base;
+    base += items(g);
+  }
+  if (t == 255u) item_first[m] = base;  // the last thread's range ends at m: the total
+}
+
+// the exact sum of members [lo, hi) on one lane; false: infinity
+__device__ TB_NOINLINE bool gs_exact(const g1a* __restrict__ pts, const uint8_t* __restrict__ code, const uint32_t* __restrict__ list,
+                                     uint32_t n_pts, uint32_t lo, uint32_t hi, g1a& o) {
+  g1j acc = jac_inf<fp>();
+  for (uint32_t j = lo; j < hi; j++) {
+    const uint32_t k = list ? list[j] : j;
+    if (k < n_pts && code[k] == 0) acc = jac_add_aff(acc, pts[k]);
+  }
+  return jac_to_aff(o, acc);
+}
+
+// out / oskip: the sum of pts[list[j]] (list nullptr: pts[j]) over lo <= j < hi with code 0 (all threads call)
+__device__ TB_INLINE void gs_sum(ka_set& S, const g1a* __restrict__ pts, const uint8_t* __restrict__ code, const uint32_t* __restrict__ list,
+                                 uint32_t n_pts, uint32_t lo, uint32_t hi, g1a* __restrict__ out, uint8_t* __restrict__ oskip, int q, int d,
+                                 const coop::cctx& K, const c32& one) {
+  if (hi <= lo + 1u) {  // no member, or one: a copy
+    if (threadIdx.x == 0) {
+      g1a o;
+      o.x = fp_zero();
+      o.y = fp_zero();
+      uint8_t sk = 1;
+      if (hi > lo) {
+        const uint32_t k = list ? list[lo] : lo;
+        if (k < n_pts && code[k] == 0) {
+          o = pts[k];
+          sk = 0;
+        }
+      }
+      *out = o;
+      *oskip = sk;
+    }
+    return;
+  }
+  coop::cj1 acc = {c32(0), c32(0), c32(0)};
+  bool inf = true;
+  for (uint32_t j = lo + (uint32_t)q; j < hi; j += KA_ROWS) {
+    const uint32_t k = list ? list[j] : j;
+    if (k >= n_pts || code[k] != 0) continue;
+    const c32 qx = crow::from_fp(pts[k].x), qy = crow::from_fp(pts[k].y);
+    if (inf) {
+      acc = {qx, qy, one};
+      inf = false;
+    } else {
+      acc = coop::madd(acc, qx, qy, K);
+    }
+  }
+  S.pt[q][0][d] = acc.x;
+  S.pt[q][1][d] = acc.y;
+  S.pt[q][2][d] = acc.z;
+  if (d == 0) S.inf[q] = inf ? 1u : 0u;
+  __syncthreads();
+  ka_tree(S, KA_ROWS, q, d, K);
+  if (q == 0) {  // 0: the coop sum stands, 1: exceptional -> the exact body, 2: no member left
+    const c32 zv[1] = {S.pt[0][2][d]};
+    const bool zero = crow::zeros_n<1>(zv, S.zb[0]) != 0u;
+    if (d == 0) S.mode = S.inf[0] != 0 ? 2 : zero ? 1 : 0;
+  }
+  __syncthreads();
+  const int mode = S.mode;
+  if (q == 0) {
+    if (mode == 0) {
+      const coop::cj1 rp = {S.pt[0][0][d], S.pt[0][1][d], S.pt[0][2][d]};
+      ka_affine(rp, S.zb[0], S.inv[0], S.out[0], d, K);
+    }
+    if (d == 0) {
+      g1a o;
+      o.x = fp_zero();
+      o.y = fp_zero();
+      uint8_t sk = 1;
+      if (mode == 0) {
+        o.x = S.out[0][0];
+        o.y = S.out[0][1];
+        sk = 0;
+      } else if (mode == 1) {
+        g1a e;
+        if (gs_exact(pts, code, list, n_pts, lo, hi, e)) {
+          o = e;
+          sk = 0;
+        }
+      }
+      *out = o;
+      *oskip = sk;
+    }
+  }
+  __syncthreads();  // S is free for the next sum
+}
+
+// pass 0: the items of every group, from the sets' points (pts, code: n of
+// them) over the CSR; pass 1: the split groups, from their items' sums (part,
+// part_skip).  item_first nullptr: no group is split (item g = group g).
+extern "C" __global__ void __launch_bounds__(KA_ROWS * 16)
+    k_group_pk_sum_coop(const g1a* __restrict__ pts, const uint8_t* __restrict__ code, uint32_t n, const uint32_t* __restrict__ grp_off,
+                        const uint32_t* __restrict__ grp_sets, const uint32_t* __restrict__ item_first, uint32_t m, uint32_t walk,
+                        uint32_t items_max, uint32_t pass, g1a* __restrict__ PG, uint8_t* __restrict__ pskip, g1a* __restrict__ part,
+                        uint8_t* __restrict__ part_skip) {
+  __shared__ ka_set S;
+  tb_latency_prio();
+  const int q = crow::row(), d = crow::dig();
+  const coop::cctx K = coop::cctx_load();
+  const c32 one = crow::from_const(R1);
+  if (pass == 0) {
+    const uint32_t total = item_first ? std::min(item_first[m], items_max) : m;
+    for (uint32_t w = blockIdx.x; w < total; w += gridDim.x) {
+      uint32_t g = w, k = 0, single = 1;
+      if (item_first) {  // the last group whose first item is <= w
+        uint32_t a = 0, b = m;
+        while (b - a > 1u) {
+          const uint32_t c = (a + b) / 2u;
+          if (item_first[c] <= w) a = c;
+          else b = c;
+        }
+        g = a;
+        k = w - item_first[g];
+        single = item_first[g + 1] - item_first[g] == 1u;
+      }
+      const uint32_t e = std::min(grp_off[g + 1], n), b0 = std::min(grp_off[g], e);
+      const uint32_t lo = std::min(e, b0 + k * walk), hi = item_first ? std::min(e, lo + walk) : e;
+      gs_sum(S, pts, code, grp_sets, n, lo, hi, single ? PG + g : part + w, single ? pskip + g : part_skip + w, q, d, K, one);
+    }
+  } else {
+    for (uint32_t g = blockIdx.x; g < m; g += gridDim.x) {
+      const uint32_t a = std::min(item_first[g], items_max), b = std::min(item_first[g + 1], items_max);
+      if (b - a < 2u) continue;
+      gs_sum(S, part, part_skip, nullptr, items_max, a, b, PG + g, pskip + g, q, d, K, one);
+    }
   }
 }

@@ -115,6 +115,9 @@ inline void tb_launch_final_recs(const uint8_t* recs, uint32_t g, hipStream_t s,
 // resident committees (k_kcoop.hip): the bad-member mask, and [r] apk of sets given as participation bit rows
 extern "C" __global__ void k_committee_mask(const uint32_t* __restrict__ members, uint32_t size, const uint8_t* __restrict__ tab_code, uint32_t tab_n, uint32_t* __restrict__ bad, uint32_t* __restrict__ valid);
 extern "C" __global__ void k_set_pk_bits_coop(const uint32_t* __restrict__ rows, uint32_t stride_w, const uint32_t* __restrict__ members, uint32_t size, const uint32_t* __restrict__ bad, const g1a* __restrict__ csum, uint32_t sum_ok, const g1a* __restrict__ tab_aff, const uint8_t* __restrict__ tab_code, uint32_t tab_n, const uint64_t* __restrict__ rand, uint32_t n, g1a* __restrict__ P, uint8_t* __restrict__ set_code, uint32_t* __restrict__ n_bad, g1a* __restrict__ P2, const g1a* __restrict__ comb, uint32_t unit_r);
+// grouped batches (k_kcoop.hip): the items of the groups (tb_plan.h group_walk), and the per-group sums of the sets' [r] apk
+extern "C" __global__ void k_group_items(const uint32_t* __restrict__ grp_off, uint32_t m, uint32_t n, uint32_t walk, uint32_t* __restrict__ item_first);
+extern "C" __global__ void k_group_pk_sum_coop(const g1a* __restrict__ pts, const uint8_t* __restrict__ code, uint32_t n, const uint32_t* __restrict__ grp_off, const uint32_t* __restrict__ grp_sets, const uint32_t* __restrict__ item_first, uint32_t m, uint32_t walk, uint32_t items_max, uint32_t pass, g1a* __restrict__ PG, uint8_t* __restrict__ pskip, g1a* __restrict__ part, uint8_t* __restrict__ part_skip);
 // k_lines.hip: the segmented accumulator with f in LDS and two lines per
 // product (tb_lines.h miller_accs_lds_body).  Measured at 131,072 sets
 // (profiles/r05_bench_acc_lds_ab.json): Miller stage alone 13.3 -> 12.6 ms

@@ -26,6 +26,7 @@
 #include "tb_pkindex.h"  // the key table's index over its key bytes: hash, probe step, probe bound
 #include "tb_plan.h"  // every host-side decision: kernel choice, pair split, product levels, workspace layout, placement
 #include "tb_pack.h"  // the staging image of a host batch: set kinds, layout, fill
+#include "tb_group.h"  // the sets of a batch grouped by message, and the grouped staging image
 
 static_assert(TB_PARTIAL_BYTES == TBLS_PARTIAL_BYTES, "partial record size");
 static_assert(tb::plan::LINE_BYTES_PER_PAIR == TB_LINE_BYTES_PER_PAIR, "tb_plan.h: line bytes per pair");
@@ -34,6 +35,7 @@ static_assert(tb::plan::HROW_SET_BYTES == sizeof(tb::hrow_set), "tb_plan.h: row-
 using tb::caller_device;
 using namespace tb::plan;
 using namespace tb::pack;
+using namespace tb::group;
 
 namespace {
 
@@ -224,23 +226,29 @@ struct partial_opts {
   const uint32_t* key_idx = nullptr;  // keys = indices into the resident table: no decompression
   bool settle = false;                // the settle layout: per-set stages and the line kernel only (pair_plan)
   const bits_src* cm = nullptr;       // the sets are bit rows over a resident committee (key_idx: the rows)
+  // A grouped launch (n_msgs < b.n; tb_group.h): b.msgs / b.msg_off hold the
+  // n_msgs distinct messages, and the CSR (device memory) lists each one's sets.
+  uint32_t n_msgs = 0;
+  const uint32_t *grp_off = nullptr, *grp_sets = nullptr;
 };
 
 // The regions of a ws_layout as typed pointers into the workspace at w.
 struct ws_ptrs {
-  g1a *pk_aff, *P;
+  g1a *pk_aff, *P, *set_P, *grp_part;
   g2a *Q, *sig_aff;
-  uint8_t *pk_code, *skip, *set_code, *sig_code, *sig_use;
-  uint32_t *msm_cnt, *msm_off, *msm_cur, *msm_idx, *mlist, *mcnt, *n_bad;
+  uint8_t *pk_code, *skip, *set_code, *sig_code, *sig_use, *pair_code, *grp_pskip;
+  uint32_t *msm_cnt, *msm_off, *msm_cur, *msm_idx, *mlist, *mcnt, *n_bad, *grp_item;
   g2j* msm_sum;
   hrow_set* hrow;
   uint4* lines;
   fp12 *f, *fpart, *fpart2, *segv;
   ws_ptrs(const ws_layout& L, uint8_t* w)
-      : pk_aff((g1a*)(w + L.pk_aff)), P((g1a*)(w + L.P)), Q((g2a*)(w + L.Q)), sig_aff((g2a*)(w + L.sig_aff)), pk_code(w + L.pk_code),
-        skip(w + L.skip), set_code(w + L.set_code), sig_code(w + L.sig_code), sig_use(w + L.sig_use), msm_cnt((uint32_t*)(w + L.msm_cnt)),
+      : pk_aff((g1a*)(w + L.pk_aff)), P((g1a*)(w + L.P)), set_P((g1a*)(w + L.set_P)), grp_part((g1a*)(w + L.grp_part)), Q((g2a*)(w + L.Q)),
+        sig_aff((g2a*)(w + L.sig_aff)), pk_code(w + L.pk_code), skip(w + L.skip), set_code(w + L.set_code), sig_code(w + L.sig_code),
+        sig_use(w + L.sig_use), pair_code(w + L.pair_code), grp_pskip(w + L.grp_pskip), msm_cnt((uint32_t*)(w + L.msm_cnt)),
         msm_off((uint32_t*)(w + L.msm_off)), msm_cur((uint32_t*)(w + L.msm_cur)), msm_idx((uint32_t*)(w + L.msm_idx)),
-        mlist((uint32_t*)(w + L.mlist)), mcnt((uint32_t*)(w + L.mcnt)), n_bad((uint32_t*)(w + L.n_bad)), msm_sum((g2j*)(w + L.msm_sum)),
+        mlist((uint32_t*)(w + L.mlist)), mcnt((uint32_t*)(w + L.mcnt)), n_bad((uint32_t*)(w + L.n_bad)), grp_item((uint32_t*)(w + L.grp_item)),
+        msm_sum((g2j*)(w + L.msm_sum)),
         hrow((hrow_set*)(w + L.hrow)), lines((uint4*)(w + L.lines)), f((fp12*)(w + L.f)), fpart((fp12*)(w + L.fpart)),
         fpart2((fp12*)(w + L.fpart2)), segv((fp12*)(w + L.segv)) {}
 };
@@ -378,6 +386,14 @@ struct partial_run {
   const uint32_t n = b.n;
   const dim3 blk = dim3(TB_BLOCK), g = dim3((b.n + TB_BLOCK - 1) / TB_BLOCK);  // one thread per set
   g1a* sig_P() const { return bp.pp.msm ? nullptr : W.P + n; }                 // -[r_i] g1 of the sets' signature pairs
+  // A grouped plan (tb_plan.h pair_plan): nh messages and main pairs, the
+  // signature side from pair xo on, the sets' [r_i] apk_i in a region of their
+  // own, and the pairs' own code rows (set_code / sig_code are per set there).
+  const uint32_t nh = bp.pp.n_msgs, xo = bp.pp.x_first();
+  const dim3 gh = dim3((bp.pp.n_msgs + TB_BLOCK - 1) / TB_BLOCK);  // one thread per message
+  g1a* set_P() const { return bp.pp.grouped ? W.set_P : W.P; }
+  uint8_t* code_a() const { return bp.pp.grouped ? W.pair_code : W.set_code; }
+  uint8_t* code_b() const { return bp.pp.grouped ? W.pair_code + align_up(bp.pp.n_pairs) : W.sig_code; }
 
 #define TB_EV(i, st) \
   if (o.ev) HIPCHK(hipEventRecord(o.ev[i], st))
@@ -407,11 +423,12 @@ struct partial_run {
     if (pp.msm) {
       hipLaunchKernelGGL(k_msm_bucket_tree, dim3(TB_MSM_TREE_WG), dim3(64), 0, sb, (const g2a*)W.sig_aff, (const uint8_t*)W.sig_use,
                          (const uint32_t*)W.msm_off, (const uint32_t*)W.msm_idx, W.msm_sum);
-      hipLaunchKernelGGL(k_msm_bitsum_pairs, dim3(TB_MSM_XPAIRS), dim3(64), 0, sb, (const g2j*)W.msm_sum, c.comb.as<const g1a>(), W.P + n,
-                         W.Q + n, W.skip + n);
+      hipLaunchKernelGGL(k_msm_bitsum_pairs, dim3(TB_MSM_XPAIRS), dim3(64), 0, sb, (const g2j*)W.msm_sum, c.comb.as<const g1a>(), W.P + xo,
+                         W.Q + xo, W.skip + xo);
       if (pp.n_xwave)  // their Miller loops, one wave each, on this stream: f[n_f_main ..)
-        hipLaunchKernelGGL(k_miller_wave, dim3(pp.n_xwave), dim3(64), 0, sb, (const g1a*)W.P + n, (const g2a*)W.Q + n, (const uint8_t*)W.skip + n,
-                           (const uint8_t*)W.set_code + n, (const uint8_t*)W.sig_code + n, pp.n_xwave, W.f + pp.n_f_main());
+        hipLaunchKernelGGL(k_miller_wave, dim3(pp.n_xwave), dim3(64), 0, sb, (const g1a*)W.P + xo, (const g2a*)W.Q + xo,
+                           (const uint8_t*)W.skip + xo, (const uint8_t*)code_a() + xo, (const uint8_t*)code_b() + xo, pp.n_xwave,
+                           W.f + pp.n_f_main());
     }
     TB_EV(9, sb);
     return TBLS_SUCCESS;
@@ -424,21 +441,37 @@ struct partial_run {
     if (bp.key == key_kind::bits) {
       TB_EV(1, sa);
       TB_EV(2, sa);
-      launch_set_pk_bits(sa, n, keys, *o.cm, b.rand, W.P, W.set_code, W.n_bad, sig_P(), comb, 0u);
+      launch_set_pk_bits(sa, n, keys, *o.cm, b.rand, set_P(), W.set_code, W.n_bad, sig_P(), comb, 0u);
     } else if (bp.key == key_kind::keys_coop) {  // one kernel; its time shows as stage 0
       const bool tab = keys.idx != nullptr;
       hipLaunchKernelGGL(k_keys_coop, dim3((n + 3) / 4), dim3(128), 0, sa, tab ? nullptr : b.pks, b.pk_off, tab ? keys.aff : nullptr,
-                         tab ? keys.code : nullptr, keys.idx, keys.tab_n, b.rand, n, W.P, sig_P(), W.set_code, W.n_bad, comb);
+                         tab ? keys.code : nullptr, keys.idx, keys.tab_n, b.rand, n, set_P(), sig_P(), W.set_code, W.n_bad, comb);
       TB_EV(1, sa);
       TB_EV(2, sa);
     } else {
       if (const int rc = launch_byte_keys(c, sa, b.pks, bp.n_keys, W.pk_aff, W.pk_code, pre_lookup)) return rc;
       TB_EV(1, sa);
       TB_EV(2, sa);
-      launch_set_pk(sa, n, bp.w2, bp.multi, b.pk_off, keys, b.rand, W.P, W.set_code, W.n_bad, W.mlist, W.mcnt, sig_P(), comb);
+      launch_set_pk(sa, n, bp.w2, bp.multi, b.pk_off, keys, b.rand, set_P(), W.set_code, W.n_bad, W.mlist, W.mcnt, sig_P(), comb);
     }
+    if (bp.pp.grouped) group_sums();
     TB_EV(3, sa);
     return TBLS_SUCCESS;
+  }
+
+  // --- grouped plans, on the key stream after the key stage: the main pairs'
+  // G1 side, P[g] = sum of the group's [r_i] apk_i (k_group_pk_sum_coop).  An
+  // infinite sum is flagged in the pair's first code byte, which the Miller
+  // kernels read like skip: the hash stream owns skip[g] at this time.
+  void group_sums() const {
+    const uint32_t walk = group_walk(n), items_max = group_items_max(n, nh);
+    const bool split = n > walk;  // else no group has more than one item
+    const uint32_t* item_first = split ? W.grp_item : nullptr;
+    if (split) hipLaunchKernelGGL(k_group_items, dim3(1), dim3(256), 0, sa, o.grp_off, nh, n, walk, W.grp_item);
+    for (uint32_t pass = 0; pass < (split ? 2u : 1u); pass++)
+      hipLaunchKernelGGL(k_group_pk_sum_coop, dim3(std::min<uint32_t>(pass ? nh : items_max, 4096u)), dim3(512), 0, sa, (const g1a*)W.set_P,
+                         (const uint8_t*)W.set_code, n, o.grp_off, o.grp_sets, item_first, nh, walk, items_max, pass, W.P, code_a(), W.grp_part,
+                         W.grp_pskip);
   }
 
   // --- high-priority stream: hash_to_G2 per set -------------------------------
@@ -454,37 +487,37 @@ struct partial_run {
       case hash_kind::none:
         break;
       case hash_kind::coop:
-        hipLaunchKernelGGL(k_set_hash_coop, dim3(n), dim3(256), 0, sh, b.msgs, b.msg_off, o.dst, o.dlen, n, Q, skip, (const uint64_t*)nullptr);
+        hipLaunchKernelGGL(k_set_hash_coop, dim3(nh), dim3(256), 0, sh, b.msgs, b.msg_off, o.dst, o.dlen, nh, Q, skip, (const uint64_t*)nullptr);
         break;
       case hash_kind::wave:
-        hipLaunchKernelGGL(k_set_hash_wave, dim3(n), dim3(128), 0, sh, b.msgs, b.msg_off, o.dst, o.dlen, n, Q, skip);
+        hipLaunchKernelGGL(k_set_hash_wave, dim3(nh), dim3(128), 0, sh, b.msgs, b.msg_off, o.dst, o.dlen, nh, Q, skip);
         break;
       case hash_kind::row: {
         hrow_set* H = W.hrow;
-        hipLaunchKernelGGL(k_hrow_field, g, blk, 0, sh, b.msgs, b.msg_off, o.dst, o.dlen, n, H);
-        hipLaunchKernelGGL(k_hrow_sswu, dim3((2 * n + 3) / 4), dim3(64), 0, sh, n, H);
-        hipLaunchKernelGGL(k_hrow_iso, g, blk, 0, sh, n, H);
-        hipLaunchKernelGGL(k_hrow_cof, dim3((n + 3) / 4), dim3(64), 0, sh, n, (const hrow_set*)H, Q, skip, 0);
-        hipLaunchKernelGGL(k_hrow_fix, g, blk, 0, sh, n, (const hrow_set*)H, Q, skip);
+        hipLaunchKernelGGL(k_hrow_field, gh, blk, 0, sh, b.msgs, b.msg_off, o.dst, o.dlen, nh, H);
+        hipLaunchKernelGGL(k_hrow_sswu, dim3((2 * nh + 3) / 4), dim3(64), 0, sh, nh, H);
+        hipLaunchKernelGGL(k_hrow_iso, gh, blk, 0, sh, nh, H);
+        hipLaunchKernelGGL(k_hrow_cof, dim3((nh + 3) / 4), dim3(64), 0, sh, nh, (const hrow_set*)H, Q, skip, 0);
+        hipLaunchKernelGGL(k_hrow_fix, gh, blk, 0, sh, nh, (const hrow_set*)H, Q, skip);
         break;
       }
       case hash_kind::quad:
-        hipLaunchKernelGGL(k_set_hash_quad, dim3((4 * n + TB_BLOCK - 1) / TB_BLOCK), blk, 0, sh, b.msgs, b.msg_off, o.dst, o.dlen, n, Q, skip);
+        hipLaunchKernelGGL(k_set_hash_quad, dim3((4 * nh + TB_BLOCK - 1) / TB_BLOCK), blk, 0, sh, b.msgs, b.msg_off, o.dst, o.dlen, nh, Q, skip);
         break;
       case hash_kind::duo:
-        hipLaunchKernelGGL(k_set_hash_duo, dim3((2 * n + TB_BLOCK - 1) / TB_BLOCK), blk, 0, sh, b.msgs, b.msg_off, o.dst, o.dlen, n, Q, skip);
+        hipLaunchKernelGGL(k_set_hash_duo, dim3((2 * nh + TB_BLOCK - 1) / TB_BLOCK), blk, 0, sh, b.msgs, b.msg_off, o.dst, o.dlen, nh, Q, skip);
         break;
       case hash_kind::w2:
         // the chains' affine addends wait in the line buffer (19,584 B per pair,
         // unused until the line kernel, which runs after this stream joins)
-        hipLaunchKernelGGL(k_set_hash_w2, g, blk, 0, sh, b.msgs, b.msg_off, o.dst, o.dlen, n, Q, skip, (g2a*)W.lines);
+        hipLaunchKernelGGL(k_set_hash_w2, gh, blk, 0, sh, b.msgs, b.msg_off, o.dst, o.dlen, nh, Q, skip, (g2a*)W.lines);
         break;
       case hash_kind::lane:
-        hipLaunchKernelGGL(k_set_hash, g, blk, 0, sh, b.msgs, b.msg_off, o.dst, o.dlen, n, Q, skip);
+        hipLaunchKernelGGL(k_set_hash, gh, blk, 0, sh, b.msgs, b.msg_off, o.dst, o.dlen, nh, Q, skip);
         break;
     }
     if (bp.hash == hash_kind::quad || bp.hash == hash_kind::duo || bp.hash == hash_kind::w2)  // the exact formulas for the sets it flags (skip == 2)
-      hipLaunchKernelGGL(k_set_hash_fix, g, blk, 0, sh, b.msgs, b.msg_off, o.dst, o.dlen, n, Q, skip);
+      hipLaunchKernelGGL(k_set_hash_fix, gh, blk, 0, sh, b.msgs, b.msg_off, o.dst, o.dlen, nh, Q, skip);
     TB_EV(7, sh);
     return TBLS_SUCCESS;
   }
@@ -495,7 +528,7 @@ struct partial_run {
     const uint32_t np = pp.n_pairs;
     const g1a* P = W.P;
     const g2a* Q = W.Q;
-    const uint8_t *skip = W.skip, *ca = W.set_code, *cb = W.sig_code;
+    const uint8_t *skip = W.skip, *ca = code_a(), *cb = code_b();
     TB_EV(10, s);
     if (!np) return TBLS_SUCCESS;
     if (pp.wave) {
@@ -550,7 +583,8 @@ struct partial_run {
 };
 
 int launch_partial(dev_ctx& c, const tbls_dev_batch& b, hipStream_t s, void* partial_out, ws_layout& L, const partial_opts& o) {
-  const batch_plan bp(b.n, b.n_keys, o.cm ? key_source::bits : o.key_idx ? key_source::table : key_source::bytes, o.settle);
+  const batch_plan bp(b.n, b.n_keys, o.cm ? key_source::bits : o.key_idx ? key_source::table : key_source::bytes, o.settle, plan_env::get(),
+                      o.grp_off && o.grp_sets ? o.n_msgs : 0u);
   L = ws_layout(bp);
   tb::stat_add(tb::TB_STAT_PARTIALS);
   HIPCHK(ws_acquire(c, s));
@@ -583,7 +617,7 @@ int launch_partial(dev_ctx& c, const tbls_dev_batch& b, hipStream_t s, void* par
   // bracket, for the exclusive stage times.
   const bool pre_lookup = bp.key == key_kind::decompress && bp.n_keys && pk_lookup_on(c) && !o.serial;
   const partial_run run{c, b, o, bp, W, keys, s, o.serial ? s : c.aux[0], o.serial ? s : c.aux[1], o.serial ? s : c.aux[2], late_join, pre_lookup};
-  HIPCHK(hipMemsetAsync(W.set_code, 0, 2 * align_up(bp.pp.n_pairs), s));  // set_code and sig_code (adjacent)
+  HIPCHK(hipMemsetAsync(W.set_code, 0, L.code_bytes, s));  // set_code and sig_code (adjacent; a grouped plan's pair codes after them)
   HIPCHK(hipMemsetAsync(W.n_bad, 0, 4, s));
   if (run.pre_lookup) {
     if (o.ev) HIPCHK(hipEventRecord(o.ev[0], s));  // stage 0 starts here
@@ -687,9 +721,14 @@ const uint8_t ETH2_DST[] = "BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_";
 // Stage sets[lo, hi) on device c (its lock held) and queue the partial
 // pipeline on c->stream: the 580-byte partial record lands at *dpart (device
 // memory, c->in) -- nothing is synchronized.  e_t0/e_t1 bracket the kernels.
+// gm: the grouped entries group the shard's own sets by message (tb_group.h)
+// and launch the grouped plan when it pays (tb_plan.h group_pays), with
+// GROUP_FORCE whenever a message repeats; a message that straddles a shard
+// cut simply appears in both shards.
+enum group_mode { GROUP_OFF, GROUP_AUTO, GROUP_FORCE };
 template <class SET>
 int shard_launch(dev_ctx* c, const SET* sets, size_t lo, size_t hi, const uint64_t* rand, const uint8_t* dst, uint32_t dlen,
-                 uint8_t** dpart, ws_layout& L, uint32_t* n_out, bool settle = false) {
+                 uint8_t** dpart, ws_layout& L, uint32_t* n_out, bool settle = false, group_mode gm = GROUP_OFF) {
   constexpr bool idx_mode = !std::is_same<SET, tbls_set>::value;  // keys from the table: indices, or committee bit rows
   constexpr bool bits_mode = std::is_same<SET, set_bits_i>::value;
   HIPCHK(hipSetDevice(c->dev));
@@ -697,12 +736,25 @@ int shard_launch(dev_ctx* c, const SET* sets, size_t lo, size_t hi, const uint64
   bits_src cm{};
   if constexpr (bits_mode)
     if (hi > lo) cm = committee_src(*c, sets[lo].slot);
-  packed p = pack_layout(sets, lo, hi, dlen);
+  groups G;
+  bool grouped = false;
+  if (gm != GROUP_OFF && !settle && !bits_mode) {
+    G = group_messages(sets, lo, hi);
+    grouped = group_pays((uint32_t)(hi - lo), G.m, gm == GROUP_FORCE);
+  }
+  packed_grouped p;
+  if (grouped)
+    p = pack_layout_grouped(sets, lo, hi, dlen, G);
+  else
+    static_cast<packed&>(p) = pack_layout(sets, lo, hi, dlen);
   const size_t in_total = p.total + TBLS_PARTIAL_BYTES + 256;
   hipStream_t s = c->stream;
   if (in_total > c->in.cap || in_total > c->hin.cap) HIPCHK(hipStreamSynchronize(s));  // buffers may still be read
   if (c->hin.ensure(in_total) || c->in.ensure(in_total)) return TBLS_DEVICE_ERROR;
-  pack_fill(c->hin.as<uint8_t>(), p, sets, lo, rand, dst, dlen);
+  if (grouped)
+    pack_fill_grouped(c->hin.as<uint8_t>(), p, sets, lo, rand, dst, dlen, G);
+  else
+    pack_fill(c->hin.as<uint8_t>(), p, sets, lo, rand, dst, dlen);
   HIPCHK(hipMemcpyAsync(c->in.p, c->hin.p, p.total, hipMemcpyHostToDevice, s));
   uint8_t* di = c->in.as<uint8_t>();
   tbls_dev_batch b;
@@ -721,6 +773,11 @@ int shard_launch(dev_ctx* c, const SET* sets, size_t lo, size_t hi, const uint64
   o.key_idx = idx_mode ? (const uint32_t*)(di + p.off_pks) : nullptr;
   o.settle = settle;
   o.cm = bits_mode ? &cm : nullptr;
+  if (grouped) {
+    o.n_msgs = p.m;
+    o.grp_off = (const uint32_t*)(di + p.off_grpoff);
+    o.grp_sets = (const uint32_t*)(di + p.off_grpsets);
+  }
   int rc = launch_partial(*c, b, s, *dpart, L, o);
   if (rc) return rc;
   HIPCHK(hipEventRecord(c->e_t1, s));
@@ -1055,7 +1112,7 @@ struct batch_pass {
   double device_ms = 0;      // the shards' e_t0 .. e_t1, summed
   dev_ctx* ctx(int g) const { return ctx_for(pl.dev[g]); }
 
-  int run(const SET* sets, size_t n, const uint64_t* rand, int n_gpus, int* ok) {
+  int run(const SET* sets, size_t n, const uint64_t* rand, int n_gpus, int* ok, group_mode gm = GROUP_OFF) {
     place_batch(pl, n, [&](size_t i) { return sets[i].n_pks; }, n_gpus, shard_min(), shard_knee());
     const int G = pl.G;
     for (int g = 0; g < G; g++) locks.emplace_back(ctx(g)->mu);  // only the placed devices, ascending: no deadlock
@@ -1064,7 +1121,7 @@ struct batch_pass {
     std::vector<int> rcs(G, 0);
     for_each_shard(G, [&](int g) {
       uint32_t nn;
-      rcs[g] = shard_launch(ctx(g), sets, pl.cut[g], pl.cut[g + 1], rand, ETH2_DST, 43, &dpart[g], L[g], &nn);
+      rcs[g] = shard_launch(ctx(g), sets, pl.cut[g], pl.cut[g + 1], rand, ETH2_DST, 43, &dpart[g], L[g], &nn, false, gm);
     });
     for (int g = 0; g < G; g++)
       if (rcs[g]) return rcs[g];
@@ -1255,7 +1312,7 @@ extern "C" int tbls_device_count(void) {
 }
 
 template <class SET>
-int batch_verify_impl(const SET* sets, size_t n, const uint64_t* rand, int n_gpus, int* ok, tbls_timing* t) {
+int batch_verify_impl(const SET* sets, size_t n, const uint64_t* rand, int n_gpus, int* ok, tbls_timing* t, group_mode gm = GROUP_OFF) {
   auto t0 = std::chrono::steady_clock::now();
   const caller_device keep;
   *ok = 0;
@@ -1264,8 +1321,27 @@ int batch_verify_impl(const SET* sets, size_t n, const uint64_t* rand, int n_gpu
   for (size_t i = 0; i < n; i++)
     if (sets[i].n_pks == 0) return TBLS_BAD_ARGUMENT;
   batch_pass<SET> pass;
-  if (const int rc = pass.run(sets, n, rand, n_gpus, ok)) return rc;
+  if (const int rc = pass.run(sets, n, rand, n_gpus, ok, gm)) return rc;
   pass.timing(t, t0);
+  return TBLS_SUCCESS;
+}
+
+extern "C" int tbls_batch_verify_grouped(const tbls_set* sets, size_t n, const uint64_t* rand, int n_gpus, uint32_t flags, int* ok,
+                                         tbls_timing* t) {
+  return batch_verify_impl(sets, n, rand, n_gpus, ok, t, (flags & TBLS_GROUP_FORCE) ? GROUP_FORCE : GROUP_AUTO);
+}
+
+extern "C" int tbls_batch_verify_idx_grouped(const tbls_set_idx* sets, size_t n, const uint64_t* rand, int n_gpus, uint32_t flags, int* ok,
+                                             tbls_timing* t) {
+  return batch_verify_impl(sets, n, rand, n_gpus, ok, t, (flags & TBLS_GROUP_FORCE) ? GROUP_FORCE : GROUP_AUTO);
+}
+
+extern "C" int tbls_group_plan(uint32_t n, uint32_t n_msgs, int* grouped, uint32_t* n_pairs) {
+  int g = 0;
+  uint32_t np = 0;
+  group_plan(n, n_msgs, g, np);
+  if (grouped) *grouped = g;
+  if (n_pairs) *n_pairs = np;
   return TBLS_SUCCESS;
 }
 
@@ -1878,6 +1954,21 @@ extern "C" int tbls_dev_batch_partial_idx(int device, const tbls_dev_batch* b, c
     if (!c.tab_n || !key_idx) return TBLS_BAD_ARGUMENT;
     partial_opts o{c.dstb.as<uint8_t>(), 43};
     o.key_idx = key_idx;
+    ws_layout L;
+    return launch_partial(c, *b, s, partial_out, L, o);
+  });
+}
+
+extern "C" int tbls_dev_batch_partial_grouped(int device, const tbls_dev_batch* b, const uint32_t* key_idx, uint32_t n_msgs,
+                                              const uint32_t* grp_off, const uint32_t* grp_sets, void* stream, void* partial_out) {
+  if (!b || !grp_off || !grp_sets || !n_msgs || n_msgs >= b->n) return TBLS_BAD_ARGUMENT;
+  return with_dev_stream(device, stream, [&](dev_ctx& c, hipStream_t s) -> int {
+    if (key_idx && !c.tab_n) return TBLS_BAD_ARGUMENT;
+    partial_opts o{c.dstb.as<uint8_t>(), 43};
+    o.key_idx = key_idx;
+    o.n_msgs = n_msgs;
+    o.grp_off = grp_off;
+    o.grp_sets = grp_sets;
     ws_layout L;
     return launch_partial(c, *b, s, partial_out, L, o);
   });

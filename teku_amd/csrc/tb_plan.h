@@ -87,6 +87,30 @@ constexpr size_t HROW_SET_BYTES = 864;              // sizeof(hrow_set), tb_hrow
 // vs 14.5 ms Miller stage at 131,072 sets, profiles/r04_bench_w2_masks.json
 // -- and stay at one.)
 #define TB_W2_MIN 32768u
+// Grouped batches (tb_group.h, k_kcoop.hip): sets that sign the same message
+// share one main pair.  The host entries group a batch of n sets with m
+// distinct messages when n >= group_min and 100 m <= percent n
+// (group_pays below); TBLS_GROUP_MIN = "min[,percent]" overrides (tuning).
+// Measured with tools/bench_grouped.py on device-resident batches
+// (profiles/grouped.json; ungrouped / grouped p50 of partial + final, ms):
+//   n = 128     m = n/64 2.74 / 5.13    m = n/2 2.74 / 5.12   the bucket-sum chain's fixed cost
+//   n = 512              5.36 / 5.26            5.37 / 5.31   parity
+//   n = 2,048            5.93 / 5.41            5.89 / 6.20
+//   n = 8,192            6.99 / 5.61            6.88 / 7.52
+//   n = 16,384  m = 64   8.91 / 6.40   m = 2,048 (n/8) 8.84 / 6.92
+//   n = 131,072 m = 64  35.01 / 14.03  m = 2,048 (n/64) 35.38 / 15.46
+// So grouping pays from 2,048 sets at m = n / 64 and loses at m = n / 2 at
+// every size of the sweep: the thresholds are the measured winning corner,
+// 2,048 sets and 2 percent (n / 64 is 1.56 percent).  Ratios between n / 64
+// and n / 2 are measured at 16,384 sets only (n / 8 wins there); the percent
+// can rise once they are measured at the small sizes too.
+#define TB_GROUP_MIN 2048u
+#define TB_GROUP_PERCENT 2u
+// k_group_pk_sum_coop: rows per workgroup, and the members one row walks at
+// least before a group is split over several workgroups (group_walk below)
+#define TB_GROUP_ROWS 32u
+#define TB_GROUP_WALK_MIN 8u
+#define TB_GROUP_CHIP_ROWS (256u * TB_GROUP_ROWS)  // one 512-thread workgroup per compute unit
 // Settling a failed batch (tb_lib.hip settle_sets)
 #define TB_SETTLE_FAN 16u                  // sets per group and groups per group of the next level (k_fp12_prod_wave_seg chunk)
 #define TB_SETTLE_MAX (TB_LINE_CHUNK / 2u)  // sets per settle chunk: both pairs of every set in one line chunk
@@ -111,6 +135,8 @@ struct plan_env {
   bool coop = true;
   // TBLS_SHARD_MIN = "min[,knee]" (min 0: every allowed idle device)
   uint32_t shard_min = TB_SHARD_MIN, shard_knee = TB_SHARD_KNEE;
+  // TBLS_GROUP_MIN = "min[,percent]": the host entries' grouping thresholds
+  uint32_t group_min = TB_GROUP_MIN, group_percent = TB_GROUP_PERCENT;
 
   // one parser per variable; v: the variable's value, nullptr when unset
   void parse_msm_min(const char* v) {
@@ -150,6 +176,14 @@ struct plan_env {
     shard_knee = k == 2 ? b : std::min(shard_min, (uint32_t)TB_SHARD_KNEE);
   }
 
+  void parse_group_min(const char* v) {
+    if (!v) return;
+    unsigned a = 0, b = 0;
+    const int k = sscanf(v, "%u,%u", &a, &b);
+    if (k >= 1) group_min = a;
+    if (k == 2 && b <= 100) group_percent = b;
+  }
+
   static plan_env from_environment() {
     plan_env e;
     e.parse_msm_min(getenv("TBLS_MSM_MIN"));
@@ -159,6 +193,7 @@ struct plan_env {
     e.parse_w2(getenv("TBLS_W2"));
     e.parse_coop(getenv("TBLS_COOP"));
     e.parse_shard_min(getenv("TBLS_SHARD_MIN"));
+    e.parse_group_min(getenv("TBLS_GROUP_MIN"));
     return e;
   }
   // read once, thread-safe (C++11 magic static): concurrent batch callers plan at once
@@ -292,16 +327,25 @@ inline void acc_plan(uint32_t n_main, uint32_t& per, uint32_t& nseg, const plan_
     }
   }
 }
+//
+// Grouped plan (n_msgs < n: the sets share n_msgs distinct messages): the
+// pairs are [0, n_msgs) the groups' (sum_{i in g} r_i apk_i, H(m_g)), then
+// always the TB_MSM_XPAIRS bit-sum pairs, whatever n is -- per-set signature
+// pairs would bring back n Miller loops.  x_first() is where the signature
+// side starts in the pair arrays: n, or n_msgs when grouped.
 struct pair_plan {
-  uint32_t n, n_extra, n_pairs, n_main, n_xwave, per, nseg;
-  bool msm, wave, split;
+  uint32_t n, n_msgs, n_extra, n_pairs, n_main, n_xwave, per, nseg;
+  bool grouped, msm, wave, split;
   // settle: the per-set layout a failed batch is settled on (settle_sets):
   // one signature pair per set (no bucket sums), split line / accumulator
   // kernels at every size
-  explicit pair_plan(uint32_t n_, bool settle = false, const plan_env& env = plan_env::get()) : n(n_) {
-    msm = !settle && n >= env.msm_min;
+  // n_msgs_: the distinct messages (0 or >= n: n, every set its own pair)
+  explicit pair_plan(uint32_t n_, bool settle = false, const plan_env& env = plan_env::get(), uint32_t n_msgs_ = 0) : n(n_) {
+    n_msgs = n_msgs_ && n_msgs_ < n && !settle ? n_msgs_ : n;
+    grouped = n_msgs < n;
+    msm = !settle && (grouped || n >= env.msm_min);
     n_extra = msm ? TB_MSM_XPAIRS : n;
-    n_pairs = n + n_extra;
+    n_pairs = n_msgs + n_extra;
     wave = !settle && n_pairs <= env.miller_wave_max;
     split = !wave;
     n_xwave = split && msm ? n_extra : 0u;  // bit-sum pairs on their own waves
@@ -315,7 +359,36 @@ struct pair_plan {
   uint32_t n_f_main() const { return nseg * n_groups(); }
   uint32_t n_f() const { return n_f_main() + n_xwave; }  // Miller values: accumulators (segment-major), then the wave pairs'
   uint32_t line_pairs() const { return split ? std::min(n_main, TB_LINE_CHUNK) : 0u; }
+  uint32_t x_first() const { return n_msgs; }  // the first signature-side pair
 };
+
+// Whether a host entry groups a batch of n sets with n_msgs distinct messages
+// (tbls_group_plan): never with every message distinct; with `force` whenever
+// some message repeats; else from group_min sets on, when at most
+// group_percent of n messages are distinct.
+inline bool group_pays(uint32_t n, uint32_t n_msgs, bool force, const plan_env& env = plan_env::get()) {
+  if (!n_msgs || n_msgs >= n) return false;
+  if (force) return true;
+  return n >= env.group_min && 100ull * n_msgs <= (uint64_t)env.group_percent * n;
+}
+
+// tbls_group_plan: grouped 0 never, 1 under `force` only, 2 without it as well;
+// n_pairs of the grouped plan when grouped is not 0, else of the ungrouped one
+inline void group_plan(uint32_t n, uint32_t n_msgs, int& grouped, uint32_t& n_pairs, const plan_env& env = plan_env::get()) {
+  grouped = !group_pays(n, n_msgs, true, env) ? 0 : group_pays(n, n_msgs, false, env) ? 2 : 1;
+  n_pairs = pair_plan(n, false, env, grouped ? n_msgs : 0u).n_pairs;
+}
+
+// k_group_pk_sum_coop: the members one workgroup sums (TB_GROUP_ROWS rows, each
+// walking its share), by counting: a batch of n sets fills the chip's rows
+// once when each row walks n / TB_GROUP_CHIP_ROWS members, and a walk shorter
+// than TB_GROUP_WALK_MIN additions is not worth a row tree (5 additions) and
+// an inversion of its own.  A group of more members is split into items of
+// this many, summed by a second pass; items(n, m) bounds their number.
+inline uint32_t group_walk(uint32_t n) {
+  return TB_GROUP_ROWS * std::max<uint32_t>(TB_GROUP_WALK_MIN, (n + TB_GROUP_CHIP_ROWS - 1) / TB_GROUP_CHIP_ROWS);
+}
+inline uint32_t group_items_max(uint32_t n, uint32_t m) { return m + n / group_walk(n); }
 
 // segments of the per-set accumulation of settle_sets: fill the GPU once (n threads per segment)
 inline uint32_t settle_nseg(uint32_t n) {
@@ -326,9 +399,9 @@ inline uint32_t settle_nseg(uint32_t n) {
 
 // true when the pipeline that just ran over n sets left what settle_sets needs:
 // one signature pair per set and both pairs' lines in one chunk
-inline bool settle_ready(uint32_t n, const plan_env& env = plan_env::get()) {
-  const pair_plan pp(n, false, env);
-  return pp.split && !pp.msm && 2ull * n <= TB_LINE_CHUNK;
+inline bool settle_ready(uint32_t n, const plan_env& env = plan_env::get(), uint32_t n_msgs = 0) {
+  const pair_plan pp(n, false, env, n_msgs);
+  return pp.split && !pp.msm && 2ull * n <= TB_LINE_CHUNK;  // a grouped plan is msm: never
 }
 
 // ---------------------------------------------------------------------------
@@ -430,16 +503,22 @@ struct batch_plan {
   int n_levels = 0;
   bool combine = false;
 
-  batch_plan(uint32_t n, uint32_t n_keys_in, key_source src, bool settle = false, const plan_env& env = plan_env::get())
-      : pp(n, settle, env), n_keys(src == key_source::bytes ? n_keys_in : 0u) {
+  // n_msgs (0: n): a grouped plan when below n -- the hash kind, the line
+  // group, the wave / split choice, the accumulator plan and the product
+  // levels follow from n_msgs messages and n_msgs + 64 pairs; the per-set
+  // kernels (key stage, signature check, w2) from n.
+  batch_plan(uint32_t n, uint32_t n_keys_in, key_source src, bool settle = false, const plan_env& env = plan_env::get(),
+             uint32_t n_msgs = 0)
+      : pp(n, settle, env, n_msgs), n_keys(src == key_source::bytes ? n_keys_in : 0u) {
     const bool small = n <= TB_HASH_WAVE_MAX && env.coop;
     w2 = use_w2(n, env);
-    if (!n) hash = hash_kind::none;
-    else if (n <= TB_HASH_WAVE_MAX) hash = env.coop ? hash_kind::coop : hash_kind::wave;
-    else if (n <= env.row_max) hash = hash_kind::row;
-    else if (n <= env.quad_max) hash = hash_kind::quad;
-    else if (n <= env.duo_max) hash = hash_kind::duo;
-    else hash = w2 ? hash_kind::w2 : hash_kind::lane;
+    const uint32_t nh = pp.n_msgs;  // messages to hash
+    if (!nh) hash = hash_kind::none;
+    else if (nh <= TB_HASH_WAVE_MAX) hash = env.coop ? hash_kind::coop : hash_kind::wave;
+    else if (nh <= env.row_max) hash = hash_kind::row;
+    else if (nh <= env.quad_max) hash = hash_kind::quad;
+    else if (nh <= env.duo_max) hash = hash_kind::duo;
+    else hash = use_w2(nh, env) ? hash_kind::w2 : hash_kind::lane;
     sig = pp.msm ? sig_kind::msm : small ? sig_kind::coop : sig_kind::pair;
     key = src == key_source::bits ? key_kind::bits
           : n_keys_in == n && n && small ? key_kind::keys_coop
@@ -489,6 +568,14 @@ struct batch_plan {
 struct ws_layout {
   size_t pk_aff, pk_code, P, Q, skip, set_code, sig_code, f, fpart, fpart2, segv, n_bad, result;
   size_t sig_aff, sig_use, msm_cnt, msm_off, msm_cur, msm_idx, msm_sum, mlist, mcnt, lines, hrow, total;
+  // Grouped plans only (empty otherwise): set_code and sig_code hold one byte
+  // per SET there, and the Miller kernels read a code per PAIR from pair_code
+  // (two rows of n_pairs zero bytes after sig_code; the group sums flag an
+  // infinite sum in the first row).  set_P: the sets' [r_i] apk_i; grp_item,
+  // grp_part, grp_pskip: k_group_pk_sum_coop's first item per group and the
+  // items' partial sums with their infinity flags.
+  size_t pair_code, set_P, grp_item, grp_part, grp_pskip;
+  size_t code_bytes;  // set_code .. the end of the last code row: zeroed by every launch
   uint32_t nb_f;
   ws_layout() : total(0) {}
   explicit ws_layout(const batch_plan& bp) {
@@ -501,11 +588,15 @@ struct ws_layout {
     size_t o = 0;
     pk_aff = o;   o = align_up(o + (size_t)K * sizeof(g1a));
     pk_code = o;  o = align_up(o + K);
+    const bool grouped = pp.grouped;
+    const uint32_t nc = grouped ? n : np;  // code bytes per row
     P = o;        o = align_up(o + (size_t)np * sizeof(g1a));
     Q = o;        o = align_up(o + (size_t)np * sizeof(g2a));
     skip = o;     o = align_up(o + np);
-    set_code = o; o = align_up(o + np);  // extra pairs: zero codes
-    sig_code = o; o = align_up(o + np);
+    set_code = o; o = align_up(o + nc);  // extra pairs: zero codes
+    sig_code = o; o = align_up(o + nc);
+    pair_code = o; o = grouped ? o + 2 * align_up(np) : o;
+    code_bytes = o - set_code;
     const size_t nm = msm ? n : 0;
     sig_aff = o;  o = align_up(o + nm * sizeof(g2a));
     sig_use = o;  o = align_up(o + nm);
@@ -516,16 +607,22 @@ struct ws_layout {
     msm_sum = o;  o = align_up(o + (msm ? (size_t)TB_MSM_BUCKETS * sizeof(g2j) : 0));
     mlist = o;    o = align_up(o + (size_t)n * 4);
     mcnt = o;     o = align_up(o + 4);
-    hrow = o;     o = align_up(o + (bp.hash == hash_kind::row ? (size_t)n * HROW_SET_BYTES : 0));
+    const uint32_t nh = pp.n_msgs;
+    hrow = o;     o = align_up(o + (bp.hash == hash_kind::row ? (size_t)nh * HROW_SET_BYTES : 0));
     // the line buffer; before the line kernel runs, k_set_hash_w2 parks the
     // chains' affine addends in it (a g2a per set)
-    lines = o;    o = align_up(o + std::max((size_t)pp.line_pairs() * LINE_BYTES_PER_PAIR, bp.hash == hash_kind::w2 ? (size_t)n * sizeof(g2a) : 0));
+    lines = o;    o = align_up(o + std::max((size_t)pp.line_pairs() * LINE_BYTES_PER_PAIR, bp.hash == hash_kind::w2 ? (size_t)nh * sizeof(g2a) : 0));
     f = o;        o = align_up(o + (size_t)(nf ? nf : 1) * sizeof(fp12));
     fpart = o;    o = align_up(o + (size_t)nb_f * sizeof(fp12));
     fpart2 = o;   o = align_up(o + (size_t)((nb_f + pc - 1) / pc + pp.nseg) * sizeof(fp12));
     segv = o;     o = align_up(o + (size_t)pp.nseg * sizeof(fp12));
     n_bad = o;    o = align_up(o + 4);
     result = o;   o = align_up(o + 4);
+    const uint32_t ni = grouped ? group_items_max(n, pp.n_msgs) : 0u;
+    set_P = o;     o = align_up(o + (grouped ? (size_t)n * sizeof(g1a) : 0));
+    grp_item = o;  o = align_up(o + (grouped ? ((size_t)pp.n_msgs + 1) * 4 : 0));
+    grp_part = o;  o = align_up(o + (size_t)ni * sizeof(g1a));
+    grp_pskip = o; o = align_up(o + ni);
     total = o;
   }
 };

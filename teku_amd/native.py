@@ -26,6 +26,7 @@ DEVICE_ERROR = 8
 BAD_ARGUMENT = 9
 
 PARTIAL_BYTES = 580
+GROUP_FORCE = 1  # TBLS_GROUP_FORCE: the grouped entries group whenever a message repeats
 COMMITTEE_SLOTS = 4
 COMMITTEE_MAX = 2048
 
@@ -169,6 +170,23 @@ _SIGS = {
             ctypes.POINTER(TblsTiming),
         ],
     ),
+    # grouped batches: one hash and one pairing per distinct message
+    "tbls_batch_verify_grouped": (
+        ctypes.c_int,
+        [ctypes.POINTER(TblsSet), ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int),
+         ctypes.POINTER(TblsTiming)],
+    ),
+    "tbls_batch_verify_idx_grouped": (
+        ctypes.c_int,
+        [ctypes.POINTER(TblsSetIdx), ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, ctypes.c_uint32,
+         ctypes.POINTER(ctypes.c_int), ctypes.POINTER(TblsTiming)],
+    ),
+    "tbls_dev_batch_partial_grouped": (
+        ctypes.c_int,
+        [ctypes.c_int, ctypes.POINTER(TblsDevBatch), ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_void_p],
+    ),
+    "tbls_group_plan": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint32)]),
     "tbls_fast_aggregate_verify_many_idx": (ctypes.c_int, [ctypes.POINTER(TblsSetIdx), ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]),
     "tbls_committee_load": (ctypes.c_int, [ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32]),
     "tbls_committee_size": (ctypes.c_uint32, [ctypes.c_uint32]),
@@ -340,6 +358,16 @@ def acc_plan(n_sets):
     per, nseg, split = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_int(0)
     check(L.tbls_acc_plan(n_sets, ctypes.byref(per), ctypes.byref(nseg), ctypes.byref(split)), "acc_plan")
     return per.value, nseg.value, split.value
+
+
+def group_plan(n_sets, n_msgs):
+    """What the grouped entries do with a shard of n_sets sets and n_msgs
+    distinct messages (tbls_group_plan; no device needed): (grouped, n_pairs),
+    grouped 0 never, 1 under GROUP_FORCE only, 2 without it as well."""
+    L = load_library() if _lib is None else _lib
+    grouped, n_pairs = ctypes.c_int(0), ctypes.c_uint32(0)
+    check(L.tbls_group_plan(n_sets, n_msgs, ctypes.byref(grouped), ctypes.byref(n_pairs)), "group_plan")
+    return grouped.value, n_pairs.value
 
 
 def place_plan(n, n_pks=None, n_devices=8, n_gpus=0, load=None, rr=0, shard_min=None, shard_knee=None):

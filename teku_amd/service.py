@@ -36,6 +36,13 @@ concurrent.futures.Future's lock and notify per task: 15 ms of 16,384
 set_result calls), and the batch is marshalled straight into the C set
 array.
 
+Grouped batches (`group_messages=True`, off by default): attestations of one
+slot sign the same AttestationData, so a gossip batch carries few distinct
+messages.  The happy path then calls tbls_batch_verify_grouped -- one hash and
+one pairing per distinct message where the library finds that grouping pays,
+the same verdict as the ungrouped batch -- and a batch that fails it goes to
+tbls_batch_verify_each as before, which gives the per-set verdicts and settles.
+
 Semantics kept from the reference: a full queue completes the future
 exceptionally with ServiceCapacityExceededException (verify, l.143-152);
 verify() before start() raises (assertIsRunning); a one-task failed batch is
@@ -191,6 +198,14 @@ def _hip_batch_each(sets, n_gpus=0, timing=None):
     return SetArray.from_tuples(sets).batch_verify_each(fast_multipliers(len(sets)), n_gpus=n_gpus, timing=timing)
 
 
+def _hip_batch_grouped(sets, n_gpus=0, timing=None, force=False) -> bool:
+    """The batch verdict over message groups (tbls_batch_verify_grouped)."""
+    try:
+        return SetArray.from_tuples(sets).batch_verify_grouped(fast_multipliers(len(sets)), n_gpus=n_gpus, force=force, timing=timing)
+    except ValueError:  # an empty key list in the batch: false, then settled per set
+        return False
+
+
 def default_num_threads() -> int:
     """One worker per device (the library's device count), 1 without one."""
     try:
@@ -210,12 +225,19 @@ class AggregatingSignatureVerificationService:
         batch_fn: Optional[Callable[[Sequence], bool]] = None,
         each_fn: Optional[Callable[[Sequence], List[bool]]] = None,
         batch_each_fn: Optional[Callable] = None,
+        group_messages: bool = False,
+        group_force: bool = False,
+        batch_grouped_fn: Optional[Callable] = None,
     ):
         """num_threads: workers (default: one per device for the device
         backend, 1 for a custom batch_fn).  batch_each_fn(sets, n_gpus,
         timing) -> (ok, per-set verdicts) replaces the device call of the
         default path (tbls_batch_verify_each) -- e.g. a placement simulator
-        in the CPU tests."""
+        in the CPU tests.  group_messages: the default path first calls
+        batch_grouped_fn(sets, n_gpus, timing) -> ok (tbls_batch_verify_grouped)
+        and only a failed batch goes on to batch_each_fn; group_force: the
+        library groups whenever a message repeats (TBLS_GROUP_FORCE), not
+        only where its thresholds say that grouping pays."""
         if num_threads is None:
             num_threads = default_num_threads() if batch_fn is None else 1
         self.num_threads = max(1, num_threads)
@@ -225,6 +247,10 @@ class AggregatingSignatureVerificationService:
         self._batch_fn = batch_fn or _hip_batch
         self._each_fn = each_fn or _hip_each
         self._batch_each_fn = batch_each_fn or _hip_batch_each
+        self.group_messages = group_messages
+        if batch_grouped_fn is None:
+            batch_grouped_fn = (lambda sets, n_gpus, timing: _hip_batch_grouped(sets, n_gpus, timing, True)) if group_force else _hip_batch_grouped
+        self._batch_grouped_fn = batch_grouped_fn
         self.batch_signature_tasks: "queue.Queue[SignatureTask]" = queue.Queue(maxsize=queue_capacity)
         self._cond = threading.Condition()  # every task future of this service waits on it
         self.n_gpus_log: List[int] = []  # the n_gpus each device batch was placed with
@@ -242,6 +268,10 @@ class AggregatingSignatureVerificationService:
         self.device_ms_total = 0.0
         self.host_ms_total = 0.0
         self.last_batch_timing: Optional[dict] = None
+        # group_messages: batches that went through the grouped entry, their sets and distinct messages
+        self.grouped_batches = 0
+        self.grouped_sets = 0
+        self.grouped_messages = 0
 
     # -- Service lifecycle -------------------------------------------------
     def start(self):
@@ -332,7 +362,18 @@ class AggregatingSignatureVerificationService:
             self.n_gpus_log.append(n_gpus)
             self.device_passes += 1
             t = native.TblsTiming()
-            ok, verdicts = self._batch_each_fn(all_sets, n_gpus, t)
+            ok, verdicts = False, None
+            if self.group_messages:
+                self.grouped_batches += 1
+                self.grouped_sets += len(all_sets)
+                self.grouped_messages += len({s[2] for s in all_sets})
+                ok = self._batch_grouped_fn(all_sets, n_gpus, t)
+                if not ok:  # per-set verdicts, settled as without the flag
+                    self.device_passes += 1
+                    self.device_ms_total += t.device_ms
+                    self.host_ms_total += t.total_ms
+            if not ok:
+                ok, verdicts = self._batch_each_fn(all_sets, n_gpus, t)
             self.sets_verified += len(all_sets)
             self.device_ms_total += t.device_ms
             self.host_ms_total += t.total_ms
@@ -400,6 +441,8 @@ class AggregatingSignatureVerificationService:
             "device_sets_per_s": self.sets_verified / (self.device_ms_total * 1e-3) if self.device_ms_total > 0 else None,
             "host_sets_per_s": self.sets_verified / (self.host_ms_total * 1e-3) if self.host_ms_total > 0 else None,
             "last_batch": self.last_batch_timing,
+            "grouped_batches_total": self.grouped_batches,
+            "grouped_sets_per_message": self.grouped_sets / self.grouped_messages if self.grouped_messages else None,
         }
 
     def _split(self, tasks: List[SignatureTask]):

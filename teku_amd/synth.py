@@ -196,6 +196,23 @@ class SetArray:
         native.check(rc, "tbls_batch_verify")
         return ok.value == 1
 
+    def batch_verify_grouped(self, rands: Sequence[int], n_gpus: int = 0, force: bool = False, timing: "native.TblsTiming" = None) -> bool:
+        """tbls_batch_verify_grouped: batch_verify's verdict, with one hash and
+        one pairing per distinct message when grouping pays (native.group_plan),
+        or with `force` whenever a message repeats."""
+        if isinstance(rands, np.ndarray):
+            assert rands.dtype == np.uint64 and rands.flags.c_contiguous and len(rands) >= self.n
+            rr = rands.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        else:
+            rr = (ctypes.c_uint64 * max(1, self.n))(*rands)
+        ok = ctypes.c_int(0)
+        rc = native.lib().tbls_batch_verify_grouped(self.ptr, self.n, rr, n_gpus, native.GROUP_FORCE if force else 0, ctypes.byref(ok),
+                                                     ctypes.byref(timing) if timing is not None else None)
+        if rc == native.BAD_ARGUMENT:
+            raise ValueError("empty public key list in batch")
+        native.check(rc, "tbls_batch_verify_grouped")
+        return ok.value == 1
+
     def batch_verify_each(self, rands: Sequence[int], n_gpus: int = 0, timing: "native.TblsTiming" = None):
         """(batch verdict, per-set verdicts): tbls_batch_verify_each -- the
         randomized batch, and when it fails every set's verdict settled from
