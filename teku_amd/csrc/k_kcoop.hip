@@ -62,6 +62,9 @@ __device__ TB_NOINLINE int kc_set_generic(const uint8_t* pks, const g1a* tab_aff
   return stage_set_pk_finish(acc, r, o);
 }
 
+// -[r] g1 of a set whose row held no valid single key, on one lane (neg_r_g1)
+__device__ TB_NOINLINE g1a kc_neg_r_g1(const g1a* comb, uint64_t r) { return neg_r_g1(comb, r); }
+
 // pks: 48-byte keys, or nullptr with (tab_aff, tab_code, key_idx, tab_n): keys
 // from the device-resident table.  P2 nullable.
 extern "C" __global__ void __launch_bounds__(128)
@@ -187,7 +190,11 @@ extern "C" __global__ void __launch_bounds__(128)
   if (w == 1 && d == 0 && act) {
     if (P2) {
       g1a o;
-      if (cinf) {
+      if (!single || M.code != TB_SUCCESS) {
+        // the row multiplied zeros or an invalid key: Z = 0 there zeroes the
+        // inversion both points share, so this set's -[r] g1 comes from one lane
+        o = kc_neg_r_g1(comb, rnd);
+      } else if (cinf) {
         o.x = fp_zero();
         o.y = fp_neg(fp_zero());
       } else {

@@ -93,8 +93,11 @@ def bad_sigs():
     return out
 
 
+_RNG = random.Random(23)  # seeded: a failing batch's randomizers reproduce
+
+
 def _raw(bls, pks, msgs, sigs):
-    rands = [random.getrandbits(64) | 1 for _ in sigs]
+    rands = [_RNG.getrandbits(64) | 1 for _ in sigs]
     return bls.batch_verify_raw([(p, 1, m, s) for p, m, s in zip(pks, msgs, sigs)], rands)
 
 
