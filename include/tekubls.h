@@ -374,6 +374,21 @@ int tbls_batch_verify_grouped(const tbls_set* sets, size_t n, const uint64_t* ra
 int tbls_batch_verify_idx_grouped(const tbls_set_idx* sets, size_t n, const uint64_t* rand, int n_gpus, uint32_t flags, int* ok,
                                   tbls_timing* t);
 
+/* tbls_batch_verify_each over message groups (BLS.java:185-207,275-336,
+ * AggregatingSignatureVerificationService.java:187-233): *ok, ok_per_set[] and
+ * the return code equal tbls_batch_verify_each's on the same arguments (n = 0,
+ * sets with n_pks == 0 -- verdict 0, left out, *ok 0 -- and decode failures
+ * included).  Placement, sharding and grouping as tbls_batch_verify_grouped.
+ * When the batch fails, a shard that ran the grouped pass settles its sets'
+ * verdicts from that pass's own work on its device -- the sets' [r] apk, the
+ * decoded signatures, the messages' hash points: nothing is staged, decoded or
+ * hashed again -- as the reference never re-decodes a task when it bisects a
+ * failed batch (l.206-233); a shard that ran ungrouped settles as in
+ * tbls_batch_verify_each.  Of several shards only those whose own record
+ * fails settle. */
+int tbls_batch_verify_each_grouped(const tbls_set* sets, size_t n, const uint64_t* rand, int n_gpus, uint32_t flags, int* ok, int* ok_per_set,
+                                   tbls_timing* t);
+
 /* tbls_dev_batch_partial (key_idx NULL) or tbls_dev_batch_partial_idx over
  * message groups, always grouped (BLS.java:275-336,
  * AggregatingSignatureVerificationService.java:187-227).  b->msgs and

@@ -47,6 +47,23 @@ public final class HipBatchVerifier {
   public static boolean batchVerifyEach(final List<List<BLSPublicKey>> keys, final List<Bytes> messages,
                                         final List<BLSSignature> signatures, final int nGpus, final boolean[] okPerSet,
                                         final boolean groupMessages) {
+    return batchVerifyEach(keys, messages, signatures, nGpus, okPerSet, groupMessages, false);
+  }
+
+  /*
+   * groupMessages with groupSettle: the batch is one call,
+   * tbls_batch_verify_each_grouped -- the grouped batch, and when it fails the
+   * per-set verdicts settled from the grouped pass's own work (nothing staged,
+   * decoded or hashed again), the verdicts of tbls_batch_verify_each.
+   */
+  public static boolean batchVerifyEachGrouped(final List<List<BLSPublicKey>> keys, final List<Bytes> messages,
+                                               final List<BLSSignature> signatures, final int nGpus, final boolean[] okPerSet) {
+    return batchVerifyEach(keys, messages, signatures, nGpus, okPerSet, true, true);
+  }
+
+  private static boolean batchVerifyEach(final List<List<BLSPublicKey>> keys, final List<Bytes> messages,
+                                        final List<BLSSignature> signatures, final int nGpus, final boolean[] okPerSet,
+                                        final boolean groupMessages, final boolean groupSettle) {
     final int n = keys.size();
     if (messages.size() != n || signatures.size() != n || okPerSet.length < n) {
       throw new IllegalArgumentException("Different collection sizes");
@@ -77,6 +94,17 @@ public final class HipBatchVerifier {
       rand[i] = HipBLS12381.nextBatchRandomMultiplier();
     }
     final int[] ok = new int[1];
+    if (groupMessages && groupSettle) {
+      final int[] eachGrouped = new int[n];
+      final int rcEach = TekuBlsHipGroupedEach.batchVerifyEachGrouped(pks, nPks, msgs, msgOff, sigs, rand, nGpus, 0, ok, eachGrouped);
+      if (rcEach != TekuBlsHip.SUCCESS) {
+        throw new BlsException("GPU BLS backend: batchVerifyEachGrouped failed, code " + rcEach);
+      }
+      for (int i = 0; i < n; i++) {
+        okPerSet[i] = eachGrouped[i] == 1;
+      }
+      return ok[0] == 1;
+    }
     if (groupMessages) {
       final int rcGrouped = TekuBlsHipGrouped.batchVerifyGrouped(pks, nPks, msgs, msgOff, sigs, rand, nGpus, 0, ok);
       if (rcGrouped == TekuBlsHip.SUCCESS && ok[0] == 1) {

@@ -21,6 +21,10 @@
  *     groups (tbls_batch_verify_grouped: one hash and one pairing per distinct
  *     message where grouping pays, the same verdict); only a batch that fails
  *     goes on to tbls_batch_verify_each.
+ *  5. groupSettle (opt-in, off by default; with groupMessages): the batch is
+ *     one call, tbls_batch_verify_each_grouped -- a grouped batch that fails
+ *     settles its per-set verdicts from the grouped pass's own work, with no
+ *     second staging, decoding or hashing of the sets.
  * Python mirror and tests: teku_amd/service.py, tests/test_service.py
  * (placement simulated over 8 devices), tests/test_gpu_configs.py.
  */
@@ -58,6 +62,7 @@ public class HipAggregatingSignatureVerificationService extends SignatureVerific
   private final int numThreads;
   private final int maxBatchSize;
   private final boolean groupMessages;
+  private final boolean groupSettle;
   private final BlockingQueue<Task> queue;
   private final AsyncRunner asyncRunner;
   private final Counter batchCounter;
@@ -80,7 +85,20 @@ public class HipAggregatingSignatureVerificationService extends SignatureVerific
       final int queueCapacity,
       final int maxBatchSize,
       final boolean groupMessages) {
+    this(metricsSystem, asyncRunnerFactory, completionRunner, queueCapacity, maxBatchSize, groupMessages,
+        false);
+  }
+
+  public HipAggregatingSignatureVerificationService(
+      final MetricsSystem metricsSystem,
+      final AsyncRunnerFactory asyncRunnerFactory,
+      final AsyncRunner completionRunner,
+      final int queueCapacity,
+      final int maxBatchSize,
+      final boolean groupMessages,
+      final boolean groupSettle) {
     this.groupMessages = groupMessages;
+    this.groupSettle = groupSettle;
     this.numThreads = HipBatchVerifier.deviceCount();
     this.asyncRunner = asyncRunnerFactory.create(getClass().getSimpleName(), numThreads);
     this.completionRunner = completionRunner;
@@ -182,10 +200,16 @@ public class HipAggregatingSignatureVerificationService extends SignatureVerific
     final int nGpus = queue.isEmpty() ? 0 : 1;
     final boolean batchIsValid;
     try {
-      batchIsValid =
-          allKeys.isEmpty()
-              || HipBatchVerifier.batchVerifyEach(
-                  allKeys, allMessages, allSignatures, nGpus, okPerSet, groupMessages);
+      if (groupMessages && groupSettle && !allKeys.isEmpty()) {
+        batchIsValid =
+            HipBatchVerifier.batchVerifyEachGrouped(
+                allKeys, allMessages, allSignatures, nGpus, okPerSet);
+      } else {
+        batchIsValid =
+            allKeys.isEmpty()
+                || HipBatchVerifier.batchVerifyEach(
+                    allKeys, allMessages, allSignatures, nGpus, okPerSet, groupMessages);
+      }
     } catch (RuntimeException e) {
       for (Task task : tasks) {
         task.result.completeExceptionally(e);

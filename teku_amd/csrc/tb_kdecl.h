@@ -147,6 +147,11 @@ extern "C" __global__ void k_pk_resolve(const uint8_t* __restrict__ pks, uint32_
 // settling a failed batch (k_pair.hip; tb_lib.hip settle_sets)
 extern "C" __global__ void k_group_test_coop(const fp12* __restrict__ vals, uint32_t stride, uint32_t nseg, const uint32_t* __restrict__ list, uint8_t* __restrict__ out);
 extern "C" __global__ void k_settle_mask(const uint8_t* __restrict__ set_code, uint32_t n, uint8_t* __restrict__ skip);
+// settling a failed grouped batch (k_gsettle.hip; tb_lib.hip settle_grouped): the messages' unevaluated line tables, the
+// signature pairs in CSR position order, and the accumulator over both (line 1 scaled by the set's [r] apk on load)
+extern "C" __global__ void k_gsettle_msg_lines(const g2a* __restrict__ Q, const uint8_t* __restrict__ skip, uint32_t m, uint4* __restrict__ lines);
+extern "C" __global__ void k_gsettle_prep(const uint32_t* __restrict__ grp_off, const uint32_t* __restrict__ grp_sets, uint32_t m, uint32_t n, uint32_t lo, uint32_t cn, const uint64_t* __restrict__ rand, const g1a* __restrict__ comb, const g2a* __restrict__ sig_aff, const uint8_t* __restrict__ sig_use, const uint8_t* __restrict__ set_code, const uint8_t* __restrict__ sig_code, const uint8_t* __restrict__ msg_skip, uint32_t* __restrict__ msg_of_pos, g1a* __restrict__ negr, g2a* __restrict__ sigq, uint8_t* __restrict__ sskip);
+extern "C" __global__ void k_miller_accs_gsettle(const uint4* __restrict__ mlines, uint32_t m, const uint32_t* __restrict__ msg_of_pos, const uint32_t* __restrict__ grp_sets, const g1a* __restrict__ set_P, const uint8_t* __restrict__ set_code, const uint8_t* __restrict__ sig_code, const uint8_t* __restrict__ msg_skip, const uint4* __restrict__ slines, const uint8_t* __restrict__ sskip, uint32_t lo, uint32_t cn, uint32_t n, uint32_t nseg, uint32_t g_pad, fp12* __restrict__ V);
 // lane-group cooperative mid-size kernels (k_hquad.hip): one DPP quad / one lane pair per set or pair; the one-lane line kernel at two waves per SIMD (k_w2_lines.hip)
 extern "C" __global__ void k_set_hash_quad(const uint8_t* __restrict__ msgs, const uint32_t* __restrict__ msg_off, const uint8_t* __restrict__ dst, uint32_t dlen, uint32_t n, g2a* __restrict__ Q, uint8_t* __restrict__ skip);
 extern "C" __global__ void k_miller_lines_quad(const g1a* __restrict__ P, const g2a* __restrict__ Q, const uint8_t* __restrict__ skip, const uint8_t* __restrict__ code_a, const uint8_t* __restrict__ code_b, uint32_t n, uint4* __restrict__ lines);

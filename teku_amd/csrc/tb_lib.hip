@@ -780,6 +780,12 @@ int shard_launch(dev_ctx* c, const SET* sets, size_t lo, size_t hi, const uint64
   }
   int rc = launch_partial(*c, b, s, *dpart, L, o);
   if (rc) return rc;
+  if (grouped) {  // for settle_grouped: the plan that ran, and where its CSR and randomizers lie in c->in / c->hin
+    L.ran_msgs = p.m;
+    L.in_grpoff = p.off_grpoff;
+    L.in_grpsets = p.off_grpsets;
+    L.in_rand = p.off_rand;
+  }
   HIPCHK(hipEventRecord(c->e_t1, s));
   return TBLS_SUCCESS;
 }
@@ -860,6 +866,9 @@ static int group_tests(dev_ctx* c, const fp12* vals, uint32_t stride, uint32_t n
   return TBLS_SUCCESS;
 }
 
+static int settle_tail(dev_ctx* c, uint32_t n, uint32_t nseg, uint32_t nA, uint32_t nB, fp12* V, fp12* A, fp12* B, uint32_t* dlist, uint8_t* dout,
+                       const std::vector<uint8_t>& codes, uint8_t* ok);
+
 // ok[0..n) for the n sets whose pipeline (normal and settle_ready, or the
 // settle layout) just ran on c; lock held, workspace L intact.
 static int settle_sets(dev_ctx* c, const ws_layout& L, uint32_t n, uint8_t* ok) {
@@ -869,7 +878,7 @@ static int settle_sets(dev_ctx* c, const ws_layout& L, uint32_t n, uint8_t* ok) 
   int rc = shard_codes(c, L, n, codes.data());  // synchronizes the stream
   if (rc) return rc;
   const settle_layout S(n);
-  const uint32_t F = TB_SETTLE_FAN, nseg = S.nseg, nA = S.nA, nB = S.nB;
+  const uint32_t nseg = S.nseg, nA = S.nA, nB = S.nB;
   if (c->sws.ensure(S.total)) return TBLS_DEVICE_ERROR;
   uint8_t* w = c->ws.as<uint8_t>();
   fp12 *V = c->sws.as<fp12>(S.V), *A = c->sws.as<fp12>(S.A), *B = c->sws.as<fp12>(S.B);
@@ -879,11 +888,21 @@ static int settle_sets(dev_ctx* c, const ws_layout& L, uint32_t n, uint8_t* ok) 
   hipLaunchKernelGGL(k_miller_accs_lds, dim3(nseg * g_pad / TB_BLOCK), dim3(TB_BLOCK), 0, s,
                      (const uint4*)(w + L.lines), (const uint8_t*)(w + L.skip), (const uint8_t*)(w + L.set_code), (const uint8_t*)(w + L.sig_code),
                      2u * n, 2u, nseg, g_pad, V, n);
+  return settle_tail(c, n, nseg, nA, nB, V, A, B, c->sws.as<uint32_t>(S.list), c->sws.as<uint8_t>(S.out), codes, ok);
+}
+
+// The tail of a settle, from the n per-set Miller values V (nseg segment rows,
+// queued on c's stream): two levels of wave products (TB_SETTLE_FAN values per
+// group, then groups of groups) into A and B, then the group tests top-down to
+// single sets.  codes[i] != 0: value i's set is invalid by its code alone.
+static int settle_tail(dev_ctx* c, uint32_t n, uint32_t nseg, uint32_t nA, uint32_t nB, fp12* V, fp12* A, fp12* B, uint32_t* dlist, uint8_t* dout,
+                       const std::vector<uint8_t>& codes, uint8_t* ok) {
+  const uint32_t F = TB_SETTLE_FAN;
+  hipStream_t s = c->stream;
+  int rc;
   hipLaunchKernelGGL(k_fp12_prod_wave_seg, dim3(nA, nseg), dim3(64), 0, s, (const fp12*)V, n, n, nseg, n, F, A, nA);
   hipLaunchKernelGGL(k_fp12_prod_wave_seg, dim3(nB, nseg), dim3(64), 0, s, (const fp12*)A, nA, nA, nseg, nA, F, B, nB);
   HIPCHK(hipGetLastError());
-  uint32_t* dlist = c->sws.as<uint32_t>(S.list);
-  uint8_t* dout = c->sws.as<uint8_t>(S.out);
   std::vector<uint32_t> lb(nB), la, l0;
   for (uint32_t b = 0; b < nB; b++) lb[b] = b;
   std::vector<uint8_t> pb, pa, p0;
@@ -905,6 +924,70 @@ static int settle_sets(dev_ctx* c, const ws_layout& L, uint32_t n, uint8_t* ok) 
     const uint32_t a = i / F, b = a / F;
     ok[i] = codes[i] == 0 && (pb[b] || passA[a] || leaf[i]) ? 1 : 0;
   }
+  return TBLS_SUCCESS;
+}
+
+// ok[0..n) for the n sets whose GROUPED pipeline just ran on c (L.ran_msgs
+// messages; lock held, stream idle, workspace L and the staging image in
+// c->in / c->hin intact).  The grouped pass leaves no per-set Miller lines --
+// one pair per message, the signature side as bucket sums -- but everything a
+// per-set value needs: set_P, the codes, sig_aff / sig_use, the messages' hash
+// points and the CSR.  So nothing is staged, decoded or hashed again
+// (k_gsettle.hip): the messages' line tables once, then per chunk of
+// gsettle_layout positions the signature pairs' lines (the line kernel a
+// batch of that many pairs takes) and the accumulator into V; then
+// settle_sets's tail over positions, and position t's verdict is set
+// grp_sets[t]'s.
+static int settle_grouped(dev_ctx* c, const ws_layout& L, uint32_t n, uint8_t* ok) {
+  if (!n) return TBLS_SUCCESS;
+  const uint32_t m = L.ran_msgs;
+  if (!m || m >= n) return TBLS_BAD_ARGUMENT;
+  tb::stat_add(tb::TB_STAT_SETTLE);
+  std::vector<uint8_t> codes(n);
+  int rc = shard_codes(c, L, n, codes.data());  // per set; synchronizes the stream
+  if (rc) return rc;
+  const plan_env& env = plan_env::get();
+  const gsettle_layout S(n, m, env);
+  if (c->sws.ensure(S.total)) return TBLS_DEVICE_ERROR;
+  const uint8_t* w = c->ws.as<uint8_t>();
+  const uint8_t* di = c->in.as<uint8_t>();
+  const uint32_t *grp_off = (const uint32_t*)(di + L.in_grpoff), *grp_sets = (const uint32_t*)(di + L.in_grpsets);
+  const uint32_t* pos_set = c->hin.as<uint32_t>(L.in_grpsets);  // the same CSR, host side
+  const uint64_t* rand = (const uint64_t*)(di + L.in_rand);
+  const g1a* set_P = (const g1a*)(w + L.set_P);
+  const g2a *Q = (const g2a*)(w + L.Q), *sig_aff = (const g2a*)(w + L.sig_aff);
+  const uint8_t *msg_skip = w + L.skip, *set_code = w + L.set_code, *sig_code = w + L.sig_code, *sig_use = w + L.sig_use;
+  uint4 *mlines = c->sws.as<uint4>(S.mlines), *slines = c->sws.as<uint4>(S.slines);
+  uint32_t* msg_of_pos = c->sws.as<uint32_t>(S.msg_of_pos);
+  g1a* negr = c->sws.as<g1a>(S.negr);
+  g2a* sigq = c->sws.as<g2a>(S.sigq);
+  uint8_t* sskip = c->sws.as<uint8_t>(S.sskip);
+  fp12 *V = c->sws.as<fp12>(S.V), *A = c->sws.as<fp12>(S.A), *B = c->sws.as<fp12>(S.B);
+  hipStream_t s = c->stream;
+  const dim3 blk(TB_BLOCK);
+  hipLaunchKernelGGL(k_gsettle_msg_lines, dim3((m + TB_BLOCK - 1) / TB_BLOCK), blk, 0, s, Q, msg_skip, m, mlines);
+  for (uint32_t k = 0; k < S.n_chunks; k++) {
+    const uint32_t lo = S.lo(k), cn = S.hi(k) - lo;
+    const uint32_t g_pad = (cn + TB_BLOCK - 1) / TB_BLOCK * TB_BLOCK;
+    const int lg = line_group(cn, env);
+    const auto line_kernel = lg == 4 ? k_miller_lines_quad : lg == 2 ? k_miller_lines_duo : k_miller_lines_w2;
+    hipLaunchKernelGGL(k_gsettle_prep, dim3(g_pad / TB_BLOCK), blk, 0, s, grp_off, grp_sets, m, n, lo, cn, rand, c->comb.as<const g1a>(), sig_aff,
+                       sig_use, set_code, sig_code, msg_skip, msg_of_pos, negr, sigq, sskip);
+    // the skip flag carries the codes: the same row for all three
+    hipLaunchKernelGGL(line_kernel, dim3((lg * cn + TB_BLOCK - 1) / TB_BLOCK), blk, 0, s, (const g1a*)negr, (const g2a*)sigq, (const uint8_t*)sskip,
+                       (const uint8_t*)sskip, (const uint8_t*)sskip, cn, slines);
+    hipLaunchKernelGGL(k_miller_accs_gsettle, dim3(S.nseg * g_pad / TB_BLOCK), blk, 0, s, (const uint4*)mlines, m, (const uint32_t*)msg_of_pos,
+                       grp_sets, set_P, set_code, sig_code, msg_skip, (const uint4*)slines, (const uint8_t*)sskip, lo, cn, n, S.nseg, g_pad, V);
+  }
+  HIPCHK(hipGetLastError());
+  std::vector<uint8_t> pos_code(n), pos_ok(n, 0);
+  for (uint32_t t = 0; t < n; t++) {
+    if (pos_set[t] >= n) return TBLS_DEVICE_ERROR;
+    pos_code[t] = codes[pos_set[t]];
+  }
+  rc = settle_tail(c, n, S.nseg, S.nA, S.nB, V, A, B, c->sws.as<uint32_t>(S.list), c->sws.as<uint8_t>(S.out), pos_code, pos_ok.data());
+  if (rc) return rc;
+  for (uint32_t t = 0; t < n; t++) ok[pos_set[t]] = pos_ok[t];
   return TBLS_SUCCESS;
 }
 
@@ -1109,6 +1192,7 @@ struct batch_pass {
   placed pl;  // declared first: the batch counts on its devices until the locks are gone
   std::vector<std::unique_lock<std::mutex>> locks;
   std::vector<ws_layout> L;  // per shard, of the pipeline that ran
+  std::vector<uint8_t*> dpart;  // per shard, its partial record (device memory, the shard's c->in)
   double device_ms = 0;      // the shards' e_t0 .. e_t1, summed
   dev_ctx* ctx(int g) const { return ctx_for(pl.dev[g]); }
 
@@ -1117,7 +1201,7 @@ struct batch_pass {
     const int G = pl.G;
     for (int g = 0; g < G; g++) locks.emplace_back(ctx(g)->mu);  // only the placed devices, ascending: no deadlock
     L.resize(G);
-    std::vector<uint8_t*> dpart(G, nullptr);
+    dpart.assign(G, nullptr);
     std::vector<int> rcs(G, 0);
     for_each_shard(G, [&](int g) {
       uint32_t nn;
@@ -1353,8 +1437,14 @@ extern "C" int tbls_batch_verify(const tbls_set* sets, size_t n, const uint64_t*
 // verdict settled from the batch's own work on the devices that ran it
 // (settle_range), under the pass's locks.  Sets with no keys are false and
 // left out of the batch.
-extern "C" int tbls_batch_verify_each(const tbls_set* sets_in, size_t n_in, const uint64_t* rand_in, int n_gpus, int* ok, int* ok_per_set,
-                                      tbls_timing* t) {
+// gm != GROUP_OFF (tbls_batch_verify_each_grouped): each shard groups its sets
+// as tbls_batch_verify_grouped does.  When the batch fails, a pass of several
+// shards first tests each shard's own partial record (one final
+// exponentiation per shard, on its device) and settles only the shards that
+// fail; a failed shard that ran grouped settles from the grouped pass's
+// workspace (settle_grouped), one that ran ungrouped as above.
+static int batch_verify_each_impl(const tbls_set* sets_in, size_t n_in, const uint64_t* rand_in, int n_gpus, group_mode gm, int* ok,
+                                  int* ok_per_set, tbls_timing* t) {
   auto t0 = std::chrono::steady_clock::now();
   const caller_device keep;
   if (!ok || (n_in && (!sets_in || !rand_in || !ok_per_set))) return TBLS_BAD_ARGUMENT;
@@ -1375,7 +1465,7 @@ extern "C" int tbls_batch_verify_each(const tbls_set* sets_in, size_t n_in, cons
   const size_t n = sets.size();
   if (n == 0) return TBLS_SUCCESS;
   batch_pass<tbls_set> pass;
-  if (const int rc = pass.run(sets.data(), n, rand.data(), n_gpus, ok)) return rc;
+  if (const int rc = pass.run(sets.data(), n, rand.data(), n_gpus, ok, gm)) return rc;
   std::vector<uint8_t> verdict(n, 1);
   if (!*ok) {
     const placed& pl = pass.pl;
@@ -1384,6 +1474,15 @@ extern "C" int tbls_batch_verify_each(const tbls_set* sets_in, size_t n_in, cons
       dev_ctx* c = pass.ctx(g);
       if (hipSetDevice(c->dev) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
         rcs[g] = TBLS_DEVICE_ERROR;
+        return;
+      }
+      const uint32_t ng = (uint32_t)(pl.cut[g + 1] - pl.cut[g]);
+      if (gm != GROUP_OFF && pl.G > 1) {  // this shard alone: a record that passes holds only valid sets
+        int ok_g = 0;
+        if ((rcs[g] = launch_final(*c, pass.dpart[g], 1, c->stream, &ok_g)) || ok_g) return;
+      }
+      if (pass.L[g].ran_msgs) {
+        rcs[g] = settle_grouped(c, pass.L[g], ng, verdict.data() + pl.cut[g]);
         return;
       }
       rcs[g] = settle_range(c, sets.data(), pl.cut[g], pl.cut[g + 1], rand.data(), true, pass.L[g], verdict.data() + pl.cut[g]);
@@ -1395,6 +1494,15 @@ extern "C" int tbls_batch_verify_each(const tbls_set* sets_in, size_t n_in, cons
   if (n != n_in) *ok = 0;  // a set without keys fails the whole batch as well
   pass.timing(t, t0);       // settling is in total_ms
   return TBLS_SUCCESS;
+}
+
+extern "C" int tbls_batch_verify_each(const tbls_set* sets, size_t n, const uint64_t* rand, int n_gpus, int* ok, int* ok_per_set, tbls_timing* t) {
+  return batch_verify_each_impl(sets, n, rand, n_gpus, GROUP_OFF, ok, ok_per_set, t);
+}
+
+extern "C" int tbls_batch_verify_each_grouped(const tbls_set* sets, size_t n, const uint64_t* rand, int n_gpus, uint32_t flags, int* ok,
+                                              int* ok_per_set, tbls_timing* t) {
+  return batch_verify_each_impl(sets, n, rand, n_gpus, (flags & TBLS_GROUP_FORCE) ? GROUP_FORCE : GROUP_AUTO, ok, ok_per_set, t);
 }
 
 // --------------------------------------------------------------------------

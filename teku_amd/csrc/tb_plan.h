@@ -137,6 +137,8 @@ struct plan_env {
   uint32_t shard_min = TB_SHARD_MIN, shard_knee = TB_SHARD_KNEE;
   // TBLS_GROUP_MIN = "min[,percent]": the host entries' grouping thresholds
   uint32_t group_min = TB_GROUP_MIN, group_percent = TB_GROUP_PERCENT;
+  // TBLS_GSETTLE_CHUNK: positions per chunk of settling a grouped batch (gsettle_layout; tuning)
+  uint32_t gsettle_chunk = TB_SETTLE_MAX;
 
   // one parser per variable; v: the variable's value, nullptr when unset
   void parse_msm_min(const char* v) {
@@ -184,6 +186,12 @@ struct plan_env {
     if (k == 2 && b <= 100) group_percent = b;
   }
 
+  void parse_gsettle_chunk(const char* v) {
+    if (!v) return;
+    const long c = atol(v);
+    if (c >= 1 && c <= (long)TB_LINE_CHUNK) gsettle_chunk = (uint32_t)c;
+  }
+
   static plan_env from_environment() {
     plan_env e;
     e.parse_msm_min(getenv("TBLS_MSM_MIN"));
@@ -194,6 +202,7 @@ struct plan_env {
     e.parse_coop(getenv("TBLS_COOP"));
     e.parse_shard_min(getenv("TBLS_SHARD_MIN"));
     e.parse_group_min(getenv("TBLS_GROUP_MIN"));
+    e.parse_gsettle_chunk(getenv("TBLS_GSETTLE_CHUNK"));
     return e;
   }
   // read once, thread-safe (C++11 magic static): concurrent batch callers plan at once
@@ -577,6 +586,12 @@ struct ws_layout {
   size_t pair_code, set_P, grp_item, grp_part, grp_pskip;
   size_t code_bytes;  // set_code .. the end of the last code row: zeroed by every launch
   uint32_t nb_f;
+  // Not part of the layout: set by the host launch that staged the batch
+  // (tb_lib.hip shard_launch) when the grouped plan ran -- the messages, and
+  // the byte offsets of the CSR (tb_group.h grp_off, grp_sets) and of the
+  // randomizers in the device's staging image.  settle_grouped reads them.
+  uint32_t ran_msgs = 0;  // 0: the shard ran ungrouped
+  size_t in_grpoff = 0, in_grpsets = 0, in_rand = 0;
   ws_layout() : total(0) {}
   explicit ws_layout(const batch_plan& bp) {
     const pair_plan& pp = bp.pp;
@@ -669,6 +684,45 @@ struct settle_layout {
     out = o;  o = align_up(o + n);
     total = o;
   }
+};
+
+// scratch of settling a failed grouped batch of n sets over m messages
+// (tb_lib.hip settle_grouped; byte offsets into dev_ctx::sws).  Positions are
+// the CSR's: position t is set grp_sets[t].  mlines: the m messages' line
+// tables, not evaluated at a G1 point (68 x 288 B per message, structure of
+// arrays with stride m); msg_of_pos: the message of each position (a word
+// each).  The signature side is built chunk by chunk, `chunk` positions at a
+// time: negr, the positions' -[r] g1; sigq / sskip, their signatures and skip
+// flags in position order (the line kernel's Q and skip); slines, the chunk's
+// signature line tables.  V, A, B, list, out and nseg / nA / nB: as
+// settle_layout(n), V indexed by position.
+struct gsettle_layout {
+  uint32_t n, m, chunk, n_chunks, nseg, nA, nB;
+  size_t mlines, msg_of_pos, negr, sigq, sskip, slines, V, A, B, list, out, total;
+  gsettle_layout(uint32_t n_, uint32_t m_, const plan_env& env = plan_env::get()) : n(n_), m(m_) {
+    const settle_layout S(n);
+    nseg = S.nseg;
+    nA = S.nA;
+    nB = S.nB;
+    chunk = std::max<uint32_t>(1u, std::min(n, env.gsettle_chunk));
+    n_chunks = (n + chunk - 1) / chunk;
+    size_t o = 0;
+    mlines = o;     o = align_up(o + (size_t)m * LINE_BYTES_PER_PAIR);
+    msg_of_pos = o; o = align_up(o + (size_t)n * 4);
+    negr = o;       o = align_up(o + (size_t)chunk * sizeof(g1a));
+    sigq = o;       o = align_up(o + (size_t)chunk * sizeof(g2a));
+    sskip = o;      o = align_up(o + chunk);
+    slines = o;     o = align_up(o + (size_t)chunk * LINE_BYTES_PER_PAIR);
+    V = o;          o = align_up(o + (size_t)nseg * n * sizeof(fp12));
+    A = o;          o = align_up(o + (size_t)nseg * nA * sizeof(fp12));
+    B = o;          o = align_up(o + (size_t)nseg * nB * sizeof(fp12));
+    list = o;       o = align_up(o + (size_t)n * 4);
+    out = o;        o = align_up(o + n);
+    total = o;
+  }
+  // chunk k covers positions [lo(k), hi(k))
+  uint32_t lo(uint32_t k) const { return k * chunk; }
+  uint32_t hi(uint32_t k) const { return std::min<uint64_t>(n, (uint64_t)(k + 1) * chunk); }
 };
 
 }  // namespace plan

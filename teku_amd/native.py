@@ -176,6 +176,11 @@ _SIGS = {
         [ctypes.POINTER(TblsSet), ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int),
          ctypes.POINTER(TblsTiming)],
     ),
+    "tbls_batch_verify_each_grouped": (
+        ctypes.c_int,
+        [ctypes.POINTER(TblsSet), ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int),
+         ctypes.POINTER(ctypes.c_int), ctypes.POINTER(TblsTiming)],
+    ),
     "tbls_batch_verify_idx_grouped": (
         ctypes.c_int,
         [ctypes.POINTER(TblsSetIdx), ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, ctypes.c_uint32,

@@ -42,6 +42,10 @@ messages.  The happy path then calls tbls_batch_verify_grouped -- one hash and
 one pairing per distinct message where the library finds that grouping pays,
 the same verdict as the ungrouped batch -- and a batch that fails it goes to
 tbls_batch_verify_each as before, which gives the per-set verdicts and settles.
+With `group_settle=True` as well (off by default) the batch is one call,
+tbls_batch_verify_each_grouped: a grouped batch that fails settles its per-set
+verdicts from the grouped pass's own work, with no second staging, decoding or
+hashing of the sets.
 
 Semantics kept from the reference: a full queue completes the future
 exceptionally with ServiceCapacityExceededException (verify, l.143-152);
@@ -206,6 +210,11 @@ def _hip_batch_grouped(sets, n_gpus=0, timing=None, force=False) -> bool:
         return False
 
 
+def _hip_batch_each_grouped(sets, n_gpus=0, timing=None, force=False):
+    """(batch verdict, per-set verdicts) over message groups in one device call (tbls_batch_verify_each_grouped)."""
+    return SetArray.from_tuples(sets).batch_verify_each_grouped(fast_multipliers(len(sets)), n_gpus=n_gpus, force=force, timing=timing)
+
+
 def default_num_threads() -> int:
     """One worker per device (the library's device count), 1 without one."""
     try:
@@ -228,6 +237,8 @@ class AggregatingSignatureVerificationService:
         group_messages: bool = False,
         group_force: bool = False,
         batch_grouped_fn: Optional[Callable] = None,
+        group_settle: bool = False,
+        batch_each_grouped_fn: Optional[Callable] = None,
     ):
         """num_threads: workers (default: one per device for the device
         backend, 1 for a custom batch_fn).  batch_each_fn(sets, n_gpus,
@@ -237,7 +248,11 @@ class AggregatingSignatureVerificationService:
         batch_grouped_fn(sets, n_gpus, timing) -> ok (tbls_batch_verify_grouped)
         and only a failed batch goes on to batch_each_fn; group_force: the
         library groups whenever a message repeats (TBLS_GROUP_FORCE), not
-        only where its thresholds say that grouping pays."""
+        only where its thresholds say that grouping pays.  group_settle
+        (with group_messages): the batch is one call of
+        batch_each_grouped_fn(sets, n_gpus, timing) -> (ok, per-set verdicts)
+        (tbls_batch_verify_each_grouped), which settles a failed grouped
+        batch from the grouped pass."""
         if num_threads is None:
             num_threads = default_num_threads() if batch_fn is None else 1
         self.num_threads = max(1, num_threads)
@@ -251,6 +266,11 @@ class AggregatingSignatureVerificationService:
         if batch_grouped_fn is None:
             batch_grouped_fn = (lambda sets, n_gpus, timing: _hip_batch_grouped(sets, n_gpus, timing, True)) if group_force else _hip_batch_grouped
         self._batch_grouped_fn = batch_grouped_fn
+        self.group_settle = group_settle
+        if batch_each_grouped_fn is None:
+            batch_each_grouped_fn = ((lambda sets, n_gpus, timing: _hip_batch_each_grouped(sets, n_gpus, timing, True)) if group_force
+                                     else _hip_batch_each_grouped)
+        self._batch_each_grouped_fn = batch_each_grouped_fn
         self.batch_signature_tasks: "queue.Queue[SignatureTask]" = queue.Queue(maxsize=queue_capacity)
         self._cond = threading.Condition()  # every task future of this service waits on it
         self.n_gpus_log: List[int] = []  # the n_gpus each device batch was placed with
@@ -367,12 +387,15 @@ class AggregatingSignatureVerificationService:
                 self.grouped_batches += 1
                 self.grouped_sets += len(all_sets)
                 self.grouped_messages += len({s[2] for s in all_sets})
-                ok = self._batch_grouped_fn(all_sets, n_gpus, t)
-                if not ok:  # per-set verdicts, settled as without the flag
-                    self.device_passes += 1
-                    self.device_ms_total += t.device_ms
-                    self.host_ms_total += t.total_ms
-            if not ok:
+                if self.group_settle:  # the batch and its failure path in the one grouped call
+                    ok, verdicts = self._batch_each_grouped_fn(all_sets, n_gpus, t)
+                else:
+                    ok = self._batch_grouped_fn(all_sets, n_gpus, t)
+                    if not ok:  # per-set verdicts, settled as without the flag
+                        self.device_passes += 1
+                        self.device_ms_total += t.device_ms
+                        self.host_ms_total += t.total_ms
+            if not ok and verdicts is None:
                 ok, verdicts = self._batch_each_fn(all_sets, n_gpus, t)
             self.sets_verified += len(all_sets)
             self.device_ms_total += t.device_ms

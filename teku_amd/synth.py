@@ -229,6 +229,23 @@ class SetArray:
         native.check(rc, "tbls_batch_verify_each")
         return ok.value == 1, [v == 1 for v in each[: self.n]]
 
+    def batch_verify_each_grouped(self, rands: Sequence[int], n_gpus: int = 0, force: bool = False, timing: "native.TblsTiming" = None):
+        """(batch verdict, per-set verdicts): tbls_batch_verify_each_grouped --
+        batch_verify_each's result over message groups (grouping as
+        batch_verify_grouped); a failed grouped batch settles from the grouped
+        pass's own work."""
+        if isinstance(rands, np.ndarray):
+            assert rands.dtype == np.uint64 and rands.flags.c_contiguous and len(rands) >= self.n
+            rr = rands.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        else:
+            rr = (ctypes.c_uint64 * max(1, self.n))(*rands)
+        ok = ctypes.c_int(0)
+        each = (ctypes.c_int * max(1, self.n))()
+        rc = native.lib().tbls_batch_verify_each_grouped(self.ptr, self.n, rr, n_gpus, native.GROUP_FORCE if force else 0, ctypes.byref(ok), each,
+                                                          ctypes.byref(timing) if timing is not None else None)
+        native.check(rc, "tbls_batch_verify_each_grouped")
+        return ok.value == 1, [v == 1 for v in each[: self.n]]
+
     def fast_aggregate_verify_many(self) -> List[bool]:
         ok = (ctypes.c_int * max(1, self.n))()
         native.check(native.lib().tbls_fast_aggregate_verify_many(self.ptr, self.n, ok), "tbls_fast_aggregate_verify_many")
