@@ -25,6 +25,7 @@
 #include "tb_host.h"
 #include "tb_pkindex.h"  // the key table's index over its key bytes: hash, probe step, probe bound
 #include "tb_plan.h"  // every host-side decision: kernel choice, pair split, product levels, workspace layout, placement
+#include "tb_settle.h"  // the group-test descent of settling a failed batch
 #include "tb_pack.h"  // the staging image of a host batch: set kinds, layout, fill
 #include "tb_group.h"  // the sets of a batch grouped by message, and the grouped staging image
 
@@ -367,6 +368,10 @@ int launch_byte_keys(dev_ctx& c, hipStream_t s, const uint8_t* pks, uint32_t K, 
   return TBLS_SUCCESS;
 }
 
+// The Miller line kernel of a line group (tb_plan.h line_group): a lane quad,
+// a lane pair or one lane per pair.
+inline auto line_kernel_of(int lg) { return lg == 4 ? k_miller_lines_quad : lg == 2 ? k_miller_lines_duo : k_miller_lines_w2; }
+
 // One launch_partial call: the batch, its plan, the workspace and the streams
 // of its chains.  Each chain queues on one stream, in order; launch_partial
 // forks and joins them.
@@ -538,7 +543,7 @@ struct partial_run {
     // chunks of the main pairs: G2 lines (P and T in LDS), then the Fp12
     // accumulator (segment-major values: segment j of group g at f[j * n_groups + g])
     const uint4* lines = W.lines;
-    const auto line_kernel = bp.line_group == 4 ? k_miller_lines_quad : bp.line_group == 2 ? k_miller_lines_duo : k_miller_lines_w2;  // mid-size batches: a lane group per pair
+    const auto line_kernel = line_kernel_of(bp.line_group);  // mid-size batches: a lane group per pair
     for (uint32_t lo = 0; lo < pp.n_main; lo += TB_LINE_CHUNK) {
       const uint32_t m = std::min(TB_LINE_CHUNK, pp.n_main - lo), mt = (m + pp.per - 1) / pp.per;
       hipLaunchKernelGGL(line_kernel, dim3((bp.line_group * m + TB_BLOCK - 1) / TB_BLOCK), blk, 0, s, P + lo, Q + lo, skip + lo, ca + lo, cb + lo, m,
@@ -718,19 +723,39 @@ int check_keys(const dev_ctx* c, const SET* sets, size_t lo, size_t hi) {
 
 const uint8_t ETH2_DST[] = "BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_";
 
-// Stage sets[lo, hi) on device c (its lock held) and queue the partial
-// pipeline on c->stream: the 580-byte partial record lands at *dpart (device
-// memory, c->in) -- nothing is synchronized.  e_t0/e_t1 bracket the kernels.
-// gm: the grouped entries group the shard's own sets by message (tb_group.h)
-// and launch the grouped plan when it pays (tb_plan.h group_pays), with
-// GROUP_FORCE whenever a message repeats; a message that straddles a shard
-// cut simply appears in both shards.
+// How shard_launch runs a shard.  gm: the grouped entries group the shard's
+// own sets by message (tb_group.h) and launch the grouped plan when it pays
+// (tb_plan.h group_pays), with GROUP_FORCE whenever a message repeats; a
+// message that straddles a shard cut simply appears in both shards.
 enum group_mode { GROUP_OFF, GROUP_AUTO, GROUP_FORCE };
+inline group_mode group_mode_of(uint32_t flags) { return (flags & TBLS_GROUP_FORCE) ? GROUP_FORCE : GROUP_AUTO; }
+struct shard_opts {
+  const uint8_t* dst = ETH2_DST;  // hash_to_G2 domain separation tag, host memory
+  uint32_t dlen = 43;
+  bool settle = false;  // the settle layout (partial_opts::settle): no partial record
+  group_mode gm = GROUP_OFF;
+};
+// What shard_launch leaves behind: the workspace layout of the pipeline that
+// ran, the partial record (device memory, the shard's c->in) and the sets
+// staged; when the grouped plan ran, its messages and the byte offsets of the
+// CSR (tb_group.h grp_off, grp_sets) and of the randomizers in the staging
+// image (c->in, and c->hin on the host side), for settle_grouped.
+struct shard_run {
+  ws_layout L;
+  uint8_t* dpart = nullptr;
+  uint32_t n = 0;
+  uint32_t n_msgs = 0;  // 0: the shard ran ungrouped
+  size_t in_grpoff = 0, in_grpsets = 0, in_rand = 0;
+};
+
+// Stage sets[lo, hi) on device c (its lock held) and queue the partial
+// pipeline on c->stream, filling R: the 580-byte partial record lands at
+// R.dpart -- nothing is synchronized.  e_t0/e_t1 bracket the kernels.
 template <class SET>
-int shard_launch(dev_ctx* c, const SET* sets, size_t lo, size_t hi, const uint64_t* rand, const uint8_t* dst, uint32_t dlen,
-                 uint8_t** dpart, ws_layout& L, uint32_t* n_out, bool settle = false, group_mode gm = GROUP_OFF) {
+int shard_launch(dev_ctx* c, const SET* sets, size_t lo, size_t hi, const uint64_t* rand, const shard_opts& so, shard_run& R) {
   constexpr bool idx_mode = !std::is_same<SET, tbls_set>::value;  // keys from the table: indices, or committee bit rows
   constexpr bool bits_mode = std::is_same<SET, set_bits_i>::value;
+  R = shard_run();
   HIPCHK(hipSetDevice(c->dev));
   if (const int rc = check_keys(c, sets, lo, hi)) return rc;
   bits_src cm{};
@@ -738,23 +763,23 @@ int shard_launch(dev_ctx* c, const SET* sets, size_t lo, size_t hi, const uint64
     if (hi > lo) cm = committee_src(*c, sets[lo].slot);
   groups G;
   bool grouped = false;
-  if (gm != GROUP_OFF && !settle && !bits_mode) {
+  if (so.gm != GROUP_OFF && !so.settle && !bits_mode) {
     G = group_messages(sets, lo, hi);
-    grouped = group_pays((uint32_t)(hi - lo), G.m, gm == GROUP_FORCE);
+    grouped = group_pays((uint32_t)(hi - lo), G.m, so.gm == GROUP_FORCE);
   }
   packed_grouped p;
   if (grouped)
-    p = pack_layout_grouped(sets, lo, hi, dlen, G);
+    p = pack_layout_grouped(sets, lo, hi, so.dlen, G);
   else
-    static_cast<packed&>(p) = pack_layout(sets, lo, hi, dlen);
+    static_cast<packed&>(p) = pack_layout(sets, lo, hi, so.dlen);
   const size_t in_total = p.total + TBLS_PARTIAL_BYTES + 256;
   hipStream_t s = c->stream;
   if (in_total > c->in.cap || in_total > c->hin.cap) HIPCHK(hipStreamSynchronize(s));  // buffers may still be read
   if (c->hin.ensure(in_total) || c->in.ensure(in_total)) return TBLS_DEVICE_ERROR;
   if (grouped)
-    pack_fill_grouped(c->hin.as<uint8_t>(), p, sets, lo, rand, dst, dlen, G);
+    pack_fill_grouped(c->hin.as<uint8_t>(), p, sets, lo, rand, so.dst, so.dlen, G);
   else
-    pack_fill(c->hin.as<uint8_t>(), p, sets, lo, rand, dst, dlen);
+    pack_fill(c->hin.as<uint8_t>(), p, sets, lo, rand, so.dst, so.dlen);
   HIPCHK(hipMemcpyAsync(c->in.p, c->hin.p, p.total, hipMemcpyHostToDevice, s));
   uint8_t* di = c->in.as<uint8_t>();
   tbls_dev_batch b;
@@ -766,37 +791,36 @@ int shard_launch(dev_ctx* c, const SET* sets, size_t lo, size_t hi, const uint64
   b.sigs = di + p.off_sigs;
   b.rand = (const uint64_t*)(di + p.off_rand);
   b.n = p.n;
-  *dpart = di + align_up(p.total);
-  *n_out = p.n;
+  R.dpart = di + align_up(p.total);
+  R.n = p.n;
   HIPCHK(hipEventRecord(c->e_t0, s));
-  partial_opts o{di + p.off_dst, dlen};
+  partial_opts o{di + p.off_dst, so.dlen};
   o.key_idx = idx_mode ? (const uint32_t*)(di + p.off_pks) : nullptr;
-  o.settle = settle;
+  o.settle = so.settle;
   o.cm = bits_mode ? &cm : nullptr;
   if (grouped) {
     o.n_msgs = p.m;
     o.grp_off = (const uint32_t*)(di + p.off_grpoff);
     o.grp_sets = (const uint32_t*)(di + p.off_grpsets);
+    R.n_msgs = p.m;
+    R.in_grpoff = p.off_grpoff;
+    R.in_grpsets = p.off_grpsets;
+    R.in_rand = p.off_rand;
   }
-  int rc = launch_partial(*c, b, s, *dpart, L, o);
-  if (rc) return rc;
-  if (grouped) {  // for settle_grouped: the plan that ran, and where its CSR and randomizers lie in c->in / c->hin
-    L.ran_msgs = p.m;
-    L.in_grpoff = p.off_grpoff;
-    L.in_grpsets = p.off_grpsets;
-    L.in_rand = p.off_rand;
-  }
+  if (const int rc = launch_partial(*c, b, s, R.dpart, R.L, o)) return rc;
   HIPCHK(hipEventRecord(c->e_t1, s));
   return TBLS_SUCCESS;
 }
 
-// Per-set verdict codes of the last shard_launch (set_code | sig_code; signature
+// Per-set verdict codes of the shard that R records (set_code | sig_code; signature
 // errors first: decode failures surface as BlsException), after the stream is idle.
-int shard_codes(dev_ctx* c, const ws_layout& L, uint32_t n, uint8_t* codes_host) {
+int shard_codes(dev_ctx* c, const shard_run& R, uint8_t* codes_host) {
+  const uint32_t n = R.n;
   if (!n) return TBLS_SUCCESS;
   if (c->hout.ensure(2 * (size_t)n)) return TBLS_DEVICE_ERROR;
-  HIPCHK(hipMemcpyAsync(c->hout.p, c->ws.as<uint8_t>(L.set_code), n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(c->hout.as<uint8_t>() + n, c->ws.as<uint8_t>(L.sig_code), n, hipMemcpyDeviceToHost, c->stream));
+  const ws_ptrs W(R.L, c->ws.as<uint8_t>());
+  HIPCHK(hipMemcpyAsync(c->hout.p, W.set_code, n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(c->hout.as<uint8_t>() + n, W.sig_code, n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   for (uint32_t i = 0; i < n; i++) {
     const uint8_t a = c->hout.as<uint8_t>()[i], bb = c->hout.as<uint8_t>()[n + i];
@@ -813,14 +837,13 @@ int verify_on_device(int d, const tbls_set* sets, size_t n, const uint64_t* rand
   dev_ctx* c = ctx_for(d);
   if (!c) return TBLS_DEVICE_ERROR;
   std::lock_guard<std::mutex> lk(c->mu);
-  uint8_t* dpart = nullptr;
-  ws_layout L;
-  uint32_t nn = 0;
-  int rc = shard_launch(c, sets, 0, n, rand, dst, dlen, &dpart, L, &nn);
+  const shard_opts so{dst, dlen};
+  shard_run R;
+  int rc = shard_launch(c, sets, 0, n, rand, so, R);
   if (rc) return rc;
-  rc = launch_final(*c, dpart, 1, c->stream, ok);  // synchronizes c->stream
+  rc = launch_final(*c, R.dpart, 1, c->stream, ok);  // synchronizes c->stream
   if (rc) return rc;
-  return codes_host ? shard_codes(c, L, nn, codes_host) : TBLS_SUCCESS;
+  return codes_host ? shard_codes(c, R, codes_host) : TBLS_SUCCESS;
 }
 
 // ---------------------------------------------------------------------------
@@ -851,12 +874,10 @@ int verify_on_device(int d, const tbls_set* sets, size_t n, const uint64_t* rand
 // settle layout (pair_plan settle: one signature pair per set, split
 // kernels), which runs the per-set stages and the line kernel only.
 // ---------------------------------------------------------------------------
-// Group tests of the listed groups of a segmented value array on c's stream:
-// pass[k] = 1 iff group list[k] tests 1.
+// Group tests of the listed groups (at least one) of a segmented value array
+// on c's stream: pass[k] = 1 iff group list[k] tests 1.
 static int group_tests(dev_ctx* c, const fp12* vals, uint32_t stride, uint32_t nseg, const std::vector<uint32_t>& list, uint32_t* dlist,
                        uint8_t* dout, std::vector<uint8_t>& pass) {
-  pass.assign(list.size(), 0);
-  if (list.empty()) return TBLS_SUCCESS;
   hipStream_t s = c->stream;
   HIPCHK(hipMemcpyAsync(dlist, list.data(), 4 * list.size(), hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_group_test_coop, dim3((uint32_t)list.size()), dim3(TB_CFE_THREADS), 0, s, vals, stride, nseg, (const uint32_t*)dlist, dout);
@@ -866,70 +887,50 @@ static int group_tests(dev_ctx* c, const fp12* vals, uint32_t stride, uint32_t n
   return TBLS_SUCCESS;
 }
 
-static int settle_tail(dev_ctx* c, uint32_t n, uint32_t nseg, uint32_t nA, uint32_t nB, fp12* V, fp12* A, fp12* B, uint32_t* dlist, uint8_t* dout,
-                       const std::vector<uint8_t>& codes, uint8_t* ok);
-
-// ok[0..n) for the n sets whose pipeline (normal and settle_ready, or the
-// settle layout) just ran on c; lock held, workspace L intact.
-static int settle_sets(dev_ctx* c, const ws_layout& L, uint32_t n, uint8_t* ok) {
-  if (!n) return TBLS_SUCCESS;
-  tb::stat_add(tb::TB_STAT_SETTLE);
-  std::vector<uint8_t> codes(n);
-  int rc = shard_codes(c, L, n, codes.data());  // synchronizes the stream
-  if (rc) return rc;
-  const settle_layout S(n);
-  const uint32_t nseg = S.nseg, nA = S.nA, nB = S.nB;
-  if (c->sws.ensure(S.total)) return TBLS_DEVICE_ERROR;
-  uint8_t* w = c->ws.as<uint8_t>();
+// The tail of a settle, from the S.n per-set Miller values at S.V of c->sws
+// (nseg segment rows, queued on c's stream): two levels of wave products
+// (TB_SETTLE_FAN values per group, then groups of groups) into A and B, then
+// the group tests top-down to single sets (tb_settle.h settle_descent).
+// codes[i] != 0: value i's set is invalid by its code alone.
+static int settle_tail(dev_ctx* c, const settle_layout& S, const std::vector<uint8_t>& codes, uint8_t* ok) {
+  const uint32_t F = TB_SETTLE_FAN, n = S.n, nseg = S.nseg, nA = S.nA, nB = S.nB;
   fp12 *V = c->sws.as<fp12>(S.V), *A = c->sws.as<fp12>(S.A), *B = c->sws.as<fp12>(S.B);
+  uint32_t* dlist = c->sws.as<uint32_t>(S.list);
+  uint8_t* dout = c->sws.as<uint8_t>(S.out);
   hipStream_t s = c->stream;
-  const uint32_t g_pad = (n + TB_BLOCK - 1) / TB_BLOCK * TB_BLOCK;
-  hipLaunchKernelGGL(k_settle_mask, dim3((n + 255) / 256), dim3(256), 0, s, (const uint8_t*)(w + L.set_code), n, w + L.skip);
-  hipLaunchKernelGGL(k_miller_accs_lds, dim3(nseg * g_pad / TB_BLOCK), dim3(TB_BLOCK), 0, s,
-                     (const uint4*)(w + L.lines), (const uint8_t*)(w + L.skip), (const uint8_t*)(w + L.set_code), (const uint8_t*)(w + L.sig_code),
-                     2u * n, 2u, nseg, g_pad, V, n);
-  return settle_tail(c, n, nseg, nA, nB, V, A, B, c->sws.as<uint32_t>(S.list), c->sws.as<uint8_t>(S.out), codes, ok);
-}
-
-// The tail of a settle, from the n per-set Miller values V (nseg segment rows,
-// queued on c's stream): two levels of wave products (TB_SETTLE_FAN values per
-// group, then groups of groups) into A and B, then the group tests top-down to
-// single sets.  codes[i] != 0: value i's set is invalid by its code alone.
-static int settle_tail(dev_ctx* c, uint32_t n, uint32_t nseg, uint32_t nA, uint32_t nB, fp12* V, fp12* A, fp12* B, uint32_t* dlist, uint8_t* dout,
-                       const std::vector<uint8_t>& codes, uint8_t* ok) {
-  const uint32_t F = TB_SETTLE_FAN;
-  hipStream_t s = c->stream;
-  int rc;
   hipLaunchKernelGGL(k_fp12_prod_wave_seg, dim3(nA, nseg), dim3(64), 0, s, (const fp12*)V, n, n, nseg, n, F, A, nA);
   hipLaunchKernelGGL(k_fp12_prod_wave_seg, dim3(nB, nseg), dim3(64), 0, s, (const fp12*)A, nA, nA, nseg, nA, F, B, nB);
   HIPCHK(hipGetLastError());
-  std::vector<uint32_t> lb(nB), la, l0;
-  for (uint32_t b = 0; b < nB; b++) lb[b] = b;
-  std::vector<uint8_t> pb, pa, p0;
-  if ((rc = group_tests(c, B, nB, nseg, lb, dlist, dout, pb))) return rc;
-  for (uint32_t b = 0; b < nB; b++)
-    if (!pb[b])
-      for (uint32_t a = b * F; a < std::min(nA, (b + 1) * F); a++) la.push_back(a);
-  if ((rc = group_tests(c, A, nA, nseg, la, dlist, dout, pa))) return rc;
-  std::vector<uint8_t> passA(nA, 0);
-  for (size_t k = 0; k < la.size(); k++) passA[la[k]] = pa[k];
-  for (uint32_t a : la)
-    if (!passA[a])
-      for (uint32_t i = a * F; i < std::min(n, (a + 1) * F); i++)
-        if (codes[i] == 0) l0.push_back(i);
-  if ((rc = group_tests(c, V, n, nseg, l0, dlist, dout, p0))) return rc;
-  std::vector<uint8_t> leaf(n, 0);
-  for (size_t k = 0; k < l0.size(); k++) leaf[l0[k]] = p0[k];
-  for (uint32_t i = 0; i < n; i++) {
-    const uint32_t a = i / F, b = a / F;
-    ok[i] = codes[i] == 0 && (pb[b] || passA[a] || leaf[i]) ? 1 : 0;
-  }
-  return TBLS_SUCCESS;
+  return settle_descent(S, codes, ok, [&](settle_level level, const std::vector<uint32_t>& list, std::vector<uint8_t>& pass) {
+    return level == SETTLE_B   ? group_tests(c, B, nB, nseg, list, dlist, dout, pass)
+           : level == SETTLE_A ? group_tests(c, A, nA, nseg, list, dlist, dout, pass)
+                               : group_tests(c, V, n, nseg, list, dlist, dout, pass);
+  });
 }
 
-// ok[0..n) for the n sets whose GROUPED pipeline just ran on c (L.ran_msgs
-// messages; lock held, stream idle, workspace L and the staging image in
-// c->in / c->hin intact).  The grouped pass leaves no per-set Miller lines --
+// ok[0..R.n) for the sets whose pipeline (normal and settle_ready, or the
+// settle layout) just ran on c as R records; lock held, workspace R.L intact.
+static int settle_sets(dev_ctx* c, const shard_run& R, uint8_t* ok) {
+  const uint32_t n = R.n;
+  if (!n) return TBLS_SUCCESS;
+  tb::stat_add(tb::TB_STAT_SETTLE);
+  std::vector<uint8_t> codes(n);
+  int rc = shard_codes(c, R, codes.data());  // synchronizes the stream
+  if (rc) return rc;
+  const settle_layout S(n);
+  if (c->sws.ensure(S.total)) return TBLS_DEVICE_ERROR;
+  const ws_ptrs W(R.L, c->ws.as<uint8_t>());
+  hipStream_t s = c->stream;
+  const uint32_t g_pad = (n + TB_BLOCK - 1) / TB_BLOCK * TB_BLOCK;
+  hipLaunchKernelGGL(k_settle_mask, dim3((n + 255) / 256), dim3(256), 0, s, (const uint8_t*)W.set_code, n, W.skip);
+  hipLaunchKernelGGL(k_miller_accs_lds, dim3(S.nseg * g_pad / TB_BLOCK), dim3(TB_BLOCK), 0, s, (const uint4*)W.lines, (const uint8_t*)W.skip,
+                     (const uint8_t*)W.set_code, (const uint8_t*)W.sig_code, 2u * n, 2u, S.nseg, g_pad, c->sws.as<fp12>(S.V), n);
+  return settle_tail(c, S, codes, ok);
+}
+
+// ok[0..R.n) for the sets whose GROUPED pipeline just ran on c as R records
+// (R.n_msgs messages; lock held, stream idle, workspace R.L and the staging
+// image in c->in / c->hin intact).  The grouped pass leaves no per-set Miller lines --
 // one pair per message, the signature side as bucket sums -- but everything a
 // per-set value needs: set_P, the codes, sig_aff / sig_use, the messages' hash
 // points and the CSR.  So nothing is staged, decoded or hashed again
@@ -938,31 +939,32 @@ static int settle_tail(dev_ctx* c, uint32_t n, uint32_t nseg, uint32_t nA, uint3
 // batch of that many pairs takes) and the accumulator into V; then
 // settle_sets's tail over positions, and position t's verdict is set
 // grp_sets[t]'s.
-static int settle_grouped(dev_ctx* c, const ws_layout& L, uint32_t n, uint8_t* ok) {
+static int settle_grouped(dev_ctx* c, const shard_run& R, uint8_t* ok) {
+  const uint32_t n = R.n, m = R.n_msgs;
   if (!n) return TBLS_SUCCESS;
-  const uint32_t m = L.ran_msgs;
   if (!m || m >= n) return TBLS_BAD_ARGUMENT;
   tb::stat_add(tb::TB_STAT_SETTLE);
   std::vector<uint8_t> codes(n);
-  int rc = shard_codes(c, L, n, codes.data());  // per set; synchronizes the stream
+  int rc = shard_codes(c, R, codes.data());  // per set; synchronizes the stream
   if (rc) return rc;
   const plan_env& env = plan_env::get();
   const gsettle_layout S(n, m, env);
   if (c->sws.ensure(S.total)) return TBLS_DEVICE_ERROR;
-  const uint8_t* w = c->ws.as<uint8_t>();
+  const ws_ptrs W(R.L, c->ws.as<uint8_t>());
   const uint8_t* di = c->in.as<uint8_t>();
-  const uint32_t *grp_off = (const uint32_t*)(di + L.in_grpoff), *grp_sets = (const uint32_t*)(di + L.in_grpsets);
-  const uint32_t* pos_set = c->hin.as<uint32_t>(L.in_grpsets);  // the same CSR, host side
-  const uint64_t* rand = (const uint64_t*)(di + L.in_rand);
-  const g1a* set_P = (const g1a*)(w + L.set_P);
-  const g2a *Q = (const g2a*)(w + L.Q), *sig_aff = (const g2a*)(w + L.sig_aff);
-  const uint8_t *msg_skip = w + L.skip, *set_code = w + L.set_code, *sig_code = w + L.sig_code, *sig_use = w + L.sig_use;
+  const uint32_t *grp_off = (const uint32_t*)(di + R.in_grpoff), *grp_sets = (const uint32_t*)(di + R.in_grpsets);
+  const uint32_t* pos_set = c->hin.as<uint32_t>(R.in_grpsets);  // the same CSR, host side
+  const uint64_t* rand = (const uint64_t*)(di + R.in_rand);
+  const g1a* set_P = W.set_P;
+  const g2a *Q = W.Q, *sig_aff = W.sig_aff;
+  const uint8_t *msg_skip = W.skip, *set_code = W.set_code, *sig_code = W.sig_code, *sig_use = W.sig_use;
   uint4 *mlines = c->sws.as<uint4>(S.mlines), *slines = c->sws.as<uint4>(S.slines);
   uint32_t* msg_of_pos = c->sws.as<uint32_t>(S.msg_of_pos);
   g1a* negr = c->sws.as<g1a>(S.negr);
   g2a* sigq = c->sws.as<g2a>(S.sigq);
   uint8_t* sskip = c->sws.as<uint8_t>(S.sskip);
-  fp12 *V = c->sws.as<fp12>(S.V), *A = c->sws.as<fp12>(S.A), *B = c->sws.as<fp12>(S.B);
+  fp12* V = c->sws.as<fp12>(S.tail.V);
+  const uint32_t nseg = S.tail.nseg;
   hipStream_t s = c->stream;
   const dim3 blk(TB_BLOCK);
   hipLaunchKernelGGL(k_gsettle_msg_lines, dim3((m + TB_BLOCK - 1) / TB_BLOCK), blk, 0, s, Q, msg_skip, m, mlines);
@@ -970,14 +972,13 @@ static int settle_grouped(dev_ctx* c, const ws_layout& L, uint32_t n, uint8_t* o
     const uint32_t lo = S.lo(k), cn = S.hi(k) - lo;
     const uint32_t g_pad = (cn + TB_BLOCK - 1) / TB_BLOCK * TB_BLOCK;
     const int lg = line_group(cn, env);
-    const auto line_kernel = lg == 4 ? k_miller_lines_quad : lg == 2 ? k_miller_lines_duo : k_miller_lines_w2;
     hipLaunchKernelGGL(k_gsettle_prep, dim3(g_pad / TB_BLOCK), blk, 0, s, grp_off, grp_sets, m, n, lo, cn, rand, c->comb.as<const g1a>(), sig_aff,
                        sig_use, set_code, sig_code, msg_skip, msg_of_pos, negr, sigq, sskip);
     // the skip flag carries the codes: the same row for all three
-    hipLaunchKernelGGL(line_kernel, dim3((lg * cn + TB_BLOCK - 1) / TB_BLOCK), blk, 0, s, (const g1a*)negr, (const g2a*)sigq, (const uint8_t*)sskip,
-                       (const uint8_t*)sskip, (const uint8_t*)sskip, cn, slines);
-    hipLaunchKernelGGL(k_miller_accs_gsettle, dim3(S.nseg * g_pad / TB_BLOCK), blk, 0, s, (const uint4*)mlines, m, (const uint32_t*)msg_of_pos,
-                       grp_sets, set_P, set_code, sig_code, msg_skip, (const uint4*)slines, (const uint8_t*)sskip, lo, cn, n, S.nseg, g_pad, V);
+    hipLaunchKernelGGL(line_kernel_of(lg), dim3((lg * cn + TB_BLOCK - 1) / TB_BLOCK), blk, 0, s, (const g1a*)negr, (const g2a*)sigq,
+                       (const uint8_t*)sskip, (const uint8_t*)sskip, (const uint8_t*)sskip, cn, slines);
+    hipLaunchKernelGGL(k_miller_accs_gsettle, dim3(nseg * g_pad / TB_BLOCK), blk, 0, s, (const uint4*)mlines, m, (const uint32_t*)msg_of_pos,
+                       grp_sets, set_P, set_code, sig_code, msg_skip, (const uint4*)slines, (const uint8_t*)sskip, lo, cn, n, nseg, g_pad, V);
   }
   HIPCHK(hipGetLastError());
   std::vector<uint8_t> pos_code(n), pos_ok(n, 0);
@@ -985,27 +986,26 @@ static int settle_grouped(dev_ctx* c, const ws_layout& L, uint32_t n, uint8_t* o
     if (pos_set[t] >= n) return TBLS_DEVICE_ERROR;
     pos_code[t] = codes[pos_set[t]];
   }
-  rc = settle_tail(c, n, S.nseg, S.nA, S.nB, V, A, B, c->sws.as<uint32_t>(S.list), c->sws.as<uint8_t>(S.out), pos_code, pos_ok.data());
+  rc = settle_tail(c, S.tail, pos_code, pos_ok.data());
   if (rc) return rc;
   for (uint32_t t = 0; t < n; t++) ok[pos_set[t]] = pos_ok[t];
   return TBLS_SUCCESS;
 }
 
-// settle sets [lo, hi) of `sets` on c (lock held) after their batch failed:
-// from the batch's workspace when it is settle_ready (reuse = the batch ran
-// exactly these sets), else re-staged in the settle layout chunk by chunk
+// settle sets [lo, hi) of `sets` on c (lock held) after their batch failed
+// (ran: the record of the batch's shard over exactly these sets): from the
+// batch's workspace when it is settle_ready, else re-staged in the settle
+// layout chunk by chunk
 template <class SET>
-static int settle_range(dev_ctx* c, const SET* sets, size_t lo, size_t hi, const uint64_t* rand, bool reuse, const ws_layout& Lb,
-                        uint8_t* ok) {
-  const uint32_t n = (uint32_t)(hi - lo);
-  if (reuse && settle_ready(n)) return settle_sets(c, Lb, n, ok);
+static int settle_range(dev_ctx* c, const SET* sets, size_t lo, size_t hi, const uint64_t* rand, const shard_run& ran, uint8_t* ok) {
+  if (settle_ready(ran.n)) return settle_sets(c, ran, ok);
+  shard_opts so;
+  so.settle = true;
   for (size_t a = lo; a < hi; a += TB_SETTLE_MAX) {
     const size_t b = std::min(hi, a + (size_t)TB_SETTLE_MAX);
-    uint8_t* dpart = nullptr;
-    ws_layout L;
-    uint32_t nn = 0;
-    int rc = shard_launch(c, sets, a, b, rand, ETH2_DST, 43, &dpart, L, &nn, true);
-    if (!rc) rc = settle_sets(c, L, nn, ok + (a - lo));
+    shard_run R;
+    int rc = shard_launch(c, sets, a, b, rand, so, R);
+    if (!rc) rc = settle_sets(c, R, ok + (a - lo));
     if (rc) return rc;
   }
   return TBLS_SUCCESS;
@@ -1078,10 +1078,10 @@ const std::vector<ncclComm_t>* rccl_comms_locked(const std::vector<int>& devs, i
   return &(g_rccl.comms[mask] = cm);
 }
 
-// Device records dpart[k] (on device devs[k]'s stream, k < G) -> the root's
+// Device records runs[k].dpart (on device devs[k]'s stream, k < G) -> the root's
 // recs buffer (root = devs[0]).  Leaves the calling thread on the root device
 // (the caller's caller_device restores).
-int gather_partials(gather_mode mode, const std::vector<int>& devs, int G, const std::vector<uint8_t*>& dpart) {
+int gather_partials(gather_mode mode, const std::vector<int>& devs, int G, const std::vector<shard_run>& runs) {
   dev_ctx* c0 = ctx_for(devs[0]);
   if (mode == GATHER_RCCL) {  // an RCCL communicator needs G distinct hardware devices (TBLS_INIT_SHARE_DEVICES)
     uint64_t seen = 0;
@@ -1111,7 +1111,7 @@ int gather_partials(gather_mode mode, const std::vector<int>& devs, int G, const
         bad = 1;
         continue;
       }
-      bad |= g_rccl.Gather(dpart[g], g == 0 ? recv : nullptr, TBLS_PARTIAL_BYTES, ncclUint8, 0, (*cm)[g], c->stream) != ncclSuccess;
+      bad |= g_rccl.Gather(runs[g].dpart, g == 0 ? recv : nullptr, TBLS_PARTIAL_BYTES, ncclUint8, 0, (*cm)[g], c->stream) != ncclSuccess;
     }
     bad |= g_rccl.GroupEnd() != ncclSuccess;
     if (bad) return TBLS_DEVICE_ERROR;
@@ -1130,7 +1130,7 @@ int gather_partials(gather_mode mode, const std::vector<int>& devs, int G, const
     for (int g = 0; g < G; g++) {
       dev_ctx* c = ctx_for(devs[g]);
       HIPCHK(hipSetDevice(c->dev));
-      HIPCHK(hipMemcpyPeerAsync(recv + (size_t)g * TBLS_PARTIAL_BYTES, c0->dev, dpart[g], c->dev, TBLS_PARTIAL_BYTES, c->stream));
+      HIPCHK(hipMemcpyPeerAsync(recv + (size_t)g * TBLS_PARTIAL_BYTES, c0->dev, runs[g].dpart, c->dev, TBLS_PARTIAL_BYTES, c->stream));
       if (g) {
         HIPCHK(hipEventRecord(c->e_join[0], c->stream));
         HIPCHK(hipSetDevice(c0->dev));
@@ -1145,7 +1145,7 @@ int gather_partials(gather_mode mode, const std::vector<int>& devs, int G, const
     dev_ctx* c = ctx_for(devs[g]);
     HIPCHK(hipSetDevice(c->dev));
     if (c->hout.ensure(TBLS_PARTIAL_BYTES)) return TBLS_DEVICE_ERROR;
-    HIPCHK(hipMemcpyAsync(c->hout.p, dpart[g], TBLS_PARTIAL_BYTES, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->hout.p, runs[g].dpart, TBLS_PARTIAL_BYTES, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     memcpy(host.data() + (size_t)g * TBLS_PARTIAL_BYTES, c->hout.p, TBLS_PARTIAL_BYTES);
   }
@@ -1186,33 +1186,30 @@ void for_each_shard(int G, const FN& fn) {
 // partial records on the lowest device unless the one record is final as it
 // lies, and run the final exponentiation there.  The locks and the placement
 // last as long as the pass, so a caller can settle from the shards'
-// workspaces (L) under them.
+// workspaces (runs) under them.
 template <class SET>
 struct batch_pass {
   placed pl;  // declared first: the batch counts on its devices until the locks are gone
   std::vector<std::unique_lock<std::mutex>> locks;
-  std::vector<ws_layout> L;  // per shard, of the pipeline that ran
-  std::vector<uint8_t*> dpart;  // per shard, its partial record (device memory, the shard's c->in)
-  double device_ms = 0;      // the shards' e_t0 .. e_t1, summed
+  std::vector<shard_run> runs;  // per shard, what its launch left behind
+  double device_ms = 0;         // the shards' e_t0 .. e_t1, summed
   dev_ctx* ctx(int g) const { return ctx_for(pl.dev[g]); }
 
   int run(const SET* sets, size_t n, const uint64_t* rand, int n_gpus, int* ok, group_mode gm = GROUP_OFF) {
     place_batch(pl, n, [&](size_t i) { return sets[i].n_pks; }, n_gpus, shard_min(), shard_knee());
     const int G = pl.G;
     for (int g = 0; g < G; g++) locks.emplace_back(ctx(g)->mu);  // only the placed devices, ascending: no deadlock
-    L.resize(G);
-    dpart.assign(G, nullptr);
+    runs.resize(G);
+    shard_opts so;
+    so.gm = gm;
     std::vector<int> rcs(G, 0);
-    for_each_shard(G, [&](int g) {
-      uint32_t nn;
-      rcs[g] = shard_launch(ctx(g), sets, pl.cut[g], pl.cut[g + 1], rand, ETH2_DST, 43, &dpart[g], L[g], &nn, false, gm);
-    });
+    for_each_shard(G, [&](int g) { rcs[g] = shard_launch(ctx(g), sets, pl.cut[g], pl.cut[g + 1], rand, so, runs[g]); });
     for (int g = 0; g < G; g++)
       if (rcs[g]) return rcs[g];
     dev_ctx* root = ctx(0);
-    const void* recs = dpart[0];
+    const void* recs = runs[0].dpart;
     if (G > 1 || gather_forced()) {
-      if (const int rc = gather_partials(gather_sel(), pl.dev, G, dpart)) return rc;
+      if (const int rc = gather_partials(gather_sel(), pl.dev, G, runs)) return rc;
       recs = root->recs.p;
     }
     if (const int rc = launch_final(*root, recs, (uint32_t)G, root->stream, ok)) return rc;  // synchronizes the root's stream
@@ -1412,12 +1409,12 @@ int batch_verify_impl(const SET* sets, size_t n, const uint64_t* rand, int n_gpu
 
 extern "C" int tbls_batch_verify_grouped(const tbls_set* sets, size_t n, const uint64_t* rand, int n_gpus, uint32_t flags, int* ok,
                                          tbls_timing* t) {
-  return batch_verify_impl(sets, n, rand, n_gpus, ok, t, (flags & TBLS_GROUP_FORCE) ? GROUP_FORCE : GROUP_AUTO);
+  return batch_verify_impl(sets, n, rand, n_gpus, ok, t, group_mode_of(flags));
 }
 
 extern "C" int tbls_batch_verify_idx_grouped(const tbls_set_idx* sets, size_t n, const uint64_t* rand, int n_gpus, uint32_t flags, int* ok,
                                              tbls_timing* t) {
-  return batch_verify_impl(sets, n, rand, n_gpus, ok, t, (flags & TBLS_GROUP_FORCE) ? GROUP_FORCE : GROUP_AUTO);
+  return batch_verify_impl(sets, n, rand, n_gpus, ok, t, group_mode_of(flags));
 }
 
 extern "C" int tbls_group_plan(uint32_t n, uint32_t n_msgs, int* grouped, uint32_t* n_pairs) {
@@ -1476,16 +1473,13 @@ static int batch_verify_each_impl(const tbls_set* sets_in, size_t n_in, const ui
         rcs[g] = TBLS_DEVICE_ERROR;
         return;
       }
-      const uint32_t ng = (uint32_t)(pl.cut[g + 1] - pl.cut[g]);
+      const shard_run& R = pass.runs[g];
       if (gm != GROUP_OFF && pl.G > 1) {  // this shard alone: a record that passes holds only valid sets
         int ok_g = 0;
-        if ((rcs[g] = launch_final(*c, pass.dpart[g], 1, c->stream, &ok_g)) || ok_g) return;
+        if ((rcs[g] = launch_final(*c, R.dpart, 1, c->stream, &ok_g)) || ok_g) return;
       }
-      if (pass.L[g].ran_msgs) {
-        rcs[g] = settle_grouped(c, pass.L[g], ng, verdict.data() + pl.cut[g]);
-        return;
-      }
-      rcs[g] = settle_range(c, sets.data(), pl.cut[g], pl.cut[g + 1], rand.data(), true, pass.L[g], verdict.data() + pl.cut[g]);
+      rcs[g] = R.n_msgs ? settle_grouped(c, R, verdict.data() + pl.cut[g])
+                        : settle_range(c, sets.data(), pl.cut[g], pl.cut[g + 1], rand.data(), R, verdict.data() + pl.cut[g]);
     });
     for (int g = 0; g < pl.G; g++)
       if (rcs[g]) return rcs[g];
@@ -1502,7 +1496,7 @@ extern "C" int tbls_batch_verify_each(const tbls_set* sets, size_t n, const uint
 
 extern "C" int tbls_batch_verify_each_grouped(const tbls_set* sets, size_t n, const uint64_t* rand, int n_gpus, uint32_t flags, int* ok,
                                               int* ok_per_set, tbls_timing* t) {
-  return batch_verify_each_impl(sets, n, rand, n_gpus, (flags & TBLS_GROUP_FORCE) ? GROUP_FORCE : GROUP_AUTO, ok, ok_per_set, t);
+  return batch_verify_each_impl(sets, n, rand, n_gpus, group_mode_of(flags), ok, ok_per_set, t);
 }
 
 // --------------------------------------------------------------------------

@@ -586,12 +586,9 @@ struct ws_layout {
   size_t pair_code, set_P, grp_item, grp_part, grp_pskip;
   size_t code_bytes;  // set_code .. the end of the last code row: zeroed by every launch
   uint32_t nb_f;
-  // Not part of the layout: set by the host launch that staged the batch
-  // (tb_lib.hip shard_launch) when the grouped plan ran -- the messages, and
-  // the byte offsets of the CSR (tb_group.h grp_off, grp_sets) and of the
-  // randomizers in the device's staging image.  settle_grouped reads them.
-  uint32_t ran_msgs = 0;  // 0: the shard ran ungrouped
-  size_t in_grpoff = 0, in_grpsets = 0, in_rand = 0;
+  // A function of the plan alone: what a host launch knows beyond it (where
+  // the staging image holds a grouped shard's CSR and randomizers) is in the
+  // launch's own record (tb_lib.hip shard_run).
   ws_layout() : total(0) {}
   explicit ws_layout(const batch_plan& bp) {
     const pair_plan& pp = bp.pp;
@@ -664,19 +661,20 @@ struct each_layout {
   }
 };
 
-// scratch of settling n sets (tb_lib.hip settle_sets; byte offsets into
-// dev_ctx::sws): nseg segment rows of the n per-set Miller values, of their
-// nA group products (TB_SETTLE_FAN sets each) and of the nB products of those
-// groups; then the list of groups to test (at most n words) and the tests'
-// verdicts (a byte each)
+// scratch of settling n sets (tb_lib.hip settle_sets, settle_tail; byte
+// offsets into dev_ctx::sws, from `base` on, a multiple of 256): nseg segment
+// rows of the n per-set Miller values, of their nA group products
+// (TB_SETTLE_FAN sets each) and of the nB products of those groups; then the
+// list of groups to test (at most n words) and the tests' verdicts (a byte
+// each).  total: the end of the scratch, base included.
 struct settle_layout {
-  uint32_t nseg, nA, nB;
+  uint32_t n, nseg, nA, nB;
   size_t V, A, B, list, out, total;
-  explicit settle_layout(uint32_t n) {
+  explicit settle_layout(uint32_t n_, size_t base = 0) : n(n_) {
     nseg = settle_nseg(n);
     nA = (n + TB_SETTLE_FAN - 1) / TB_SETTLE_FAN;
     nB = (nA + TB_SETTLE_FAN - 1) / TB_SETTLE_FAN;
-    size_t o = 0;
+    size_t o = base;
     V = o;    o = align_up(o + (size_t)nseg * n * sizeof(fp12));
     A = o;    o = align_up(o + (size_t)nseg * nA * sizeof(fp12));
     B = o;    o = align_up(o + (size_t)nseg * nB * sizeof(fp12));
@@ -694,16 +692,13 @@ struct settle_layout {
 // each).  The signature side is built chunk by chunk, `chunk` positions at a
 // time: negr, the positions' -[r] g1; sigq / sskip, their signatures and skip
 // flags in position order (the line kernel's Q and skip); slines, the chunk's
-// signature line tables.  V, A, B, list, out and nseg / nA / nB: as
-// settle_layout(n), V indexed by position.
+// signature line tables.  tail: settle_layout(n) placed after slines, its V
+// indexed by position.
 struct gsettle_layout {
-  uint32_t n, m, chunk, n_chunks, nseg, nA, nB;
-  size_t mlines, msg_of_pos, negr, sigq, sskip, slines, V, A, B, list, out, total;
-  gsettle_layout(uint32_t n_, uint32_t m_, const plan_env& env = plan_env::get()) : n(n_), m(m_) {
-    const settle_layout S(n);
-    nseg = S.nseg;
-    nA = S.nA;
-    nB = S.nB;
+  uint32_t n, m, chunk, n_chunks;
+  size_t mlines, msg_of_pos, negr, sigq, sskip, slines, total;
+  settle_layout tail;
+  gsettle_layout(uint32_t n_, uint32_t m_, const plan_env& env = plan_env::get()) : n(n_), m(m_), tail(0) {
     chunk = std::max<uint32_t>(1u, std::min(n, env.gsettle_chunk));
     n_chunks = (n + chunk - 1) / chunk;
     size_t o = 0;
@@ -713,12 +708,8 @@ struct gsettle_layout {
     sigq = o;       o = align_up(o + (size_t)chunk * sizeof(g2a));
     sskip = o;      o = align_up(o + chunk);
     slines = o;     o = align_up(o + (size_t)chunk * LINE_BYTES_PER_PAIR);
-    V = o;          o = align_up(o + (size_t)nseg * n * sizeof(fp12));
-    A = o;          o = align_up(o + (size_t)nseg * nA * sizeof(fp12));
-    B = o;          o = align_up(o + (size_t)nseg * nB * sizeof(fp12));
-    list = o;       o = align_up(o + (size_t)n * 4);
-    out = o;        o = align_up(o + n);
-    total = o;
+    tail = settle_layout(n, o);
+    total = tail.total;
   }
   // chunk k covers positions [lo(k), hi(k))
   uint32_t lo(uint32_t k) const { return k * chunk; }

@@ -6,8 +6,8 @@
 //   * the regions are disjoint, 256-byte aligned, inside `total`, and each is
 //     as large as its contents (stated here from the element sizes);
 //   * the chunks cover [0, n) exactly once, none empty, none above `chunk`;
-//   * nseg / nA / nB and the sizes of V / A / B / list / out are
-//     settle_layout(n)'s;
+//   * the tail's nseg / nA / nB and the sizes of its V / A / B / list / out
+//     are settle_layout(n)'s;
 //   * the verdicts' position-to-set map, the CSR of tb_group.h group_messages,
 //     is a permutation of [0, n) whose positions lie inside their message's
 //     range, on interleaved and on sorted inputs;
@@ -47,14 +47,15 @@ static void check_layout(uint32_t n, uint32_t m, const plan_env& env, uint32_t w
   const settle_layout R(n);
   CHECK(S.n == n && S.m == m, "n %u m %u", n, m);
   CHECK(S.chunk == std::min(n, want_chunk), "n %u chunk %u want %u", n, S.chunk, std::min(n, want_chunk));
-  CHECK(S.nseg == R.nseg && S.nA == R.nA && S.nB == R.nB, "n %u: %u/%u/%u vs %u/%u/%u", n, S.nseg, S.nA, S.nB, R.nseg, R.nA, R.nB);
+  const settle_layout& T = S.tail;
+  CHECK(T.n == n && T.nseg == R.nseg && T.nA == R.nA && T.nB == R.nB, "n %u: %u/%u/%u vs %u/%u/%u", n, T.nseg, T.nA, T.nB, R.nseg, R.nA, R.nB);
   // the regions with their contents' sizes: 68 lines of 288 B per column, 576-byte Fp12 values, 96-byte G1 and 192-byte G2 points
   const size_t LINE = 68u * 288u, F12 = 576;
   CHECK(sizeof(fp12) == F12 && sizeof(g1a) == 96 && sizeof(g2a) == 192 && LINE_BYTES_PER_PAIR == LINE, "type sizes");
   const std::pair<size_t, size_t> reg[] = {
       {S.mlines, (size_t)m * LINE},       {S.msg_of_pos, (size_t)n * 4},      {S.negr, (size_t)S.chunk * 96}, {S.sigq, (size_t)S.chunk * 192},
-      {S.sskip, (size_t)S.chunk},         {S.slines, (size_t)S.chunk * LINE}, {S.V, (size_t)S.nseg * n * F12}, {S.A, (size_t)S.nseg * S.nA * F12},
-      {S.B, (size_t)S.nseg * S.nB * F12}, {S.list, (size_t)n * 4},            {S.out, (size_t)n}};
+      {S.sskip, (size_t)S.chunk},         {S.slines, (size_t)S.chunk * LINE}, {T.V, (size_t)T.nseg * n * F12}, {T.A, (size_t)T.nseg * T.nA * F12},
+      {T.B, (size_t)T.nseg * T.nB * F12}, {T.list, (size_t)n * 4},            {T.out, (size_t)n}};
   const size_t NR = sizeof(reg) / sizeof(reg[0]);
   for (size_t a = 0; a < NR; a++) {
     CHECK(reg[a].first % 256 == 0, "n %u m %u region %zu at %zu", n, m, a, reg[a].first);
@@ -63,8 +64,8 @@ static void check_layout(uint32_t n, uint32_t m, const plan_env& env, uint32_t w
       CHECK(reg[a].first + reg[a].second <= reg[b].first || reg[b].first + reg[b].second <= reg[a].first, "n %u m %u regions %zu and %zu overlap", n, m,
             a, b);
   }
-  CHECK(S.A - S.V == R.A - R.V && S.B - S.A == R.B - R.A && S.list - S.B == R.list - R.B && S.out - S.list == R.out - R.list &&
-            S.total - S.out == R.total - R.out,
+  CHECK(T.A - T.V == R.A - R.V && T.B - T.A == R.B - R.A && T.list - T.B == R.list - R.B && T.out - T.list == R.out - R.list &&
+            S.total - T.out == R.total - R.out && T.total == S.total,
         "n %u: the tail regions' sizes differ from settle_layout's", n);
   // the chunks
   uint64_t next = 0;
