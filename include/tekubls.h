@@ -197,6 +197,38 @@ int tbls_pk_table_resolve(const uint8_t* pks, size_t n, uint32_t* idx_out);
  * reading.  Both stay 0 without a table and with TBLS_PK_LOOKUP=0. */
 int tbls_pk_lookup_stats(uint64_t out[2], int reset);
 
+/* ---- learned key cache ----
+ * Teku memoizes a key's decompression and its validity per key object
+ * (BLSPublicKey.java:113-118, BlstPublicKey.java:74-75), so a node decodes
+ * each validator key once.  The library does the same for callers that pass
+ * key bytes and load no table: every device keeps a byte-keyed cache of the
+ * keys its key stages decompressed and found valid (TBLS_SUCCESS), with their
+ * affine points, and the same entries as above look a key up -- in the
+ * loaded table's index first, then in the cache -- before decompressing it.
+ * A hit takes the point computed from the same 48 bytes by the same code, so
+ * every result is bit for bit what it is without the cache.  The infinity
+ * key and invalid keys are never cached: they are decoded each time and fail
+ * with the same codes.  By-index and committee entries never touch the cache,
+ * and single-key batches of up to 512 sets neither read nor extend it.
+ *
+ * The capacity is fixed per process: TBLS_PK_CACHE_KEYS rows per device (read
+ * by tbls_init; default 2,097,152, about 320 MB per device, allocated by the
+ * first batch that looks keys up).  Nothing is evicted: when every row is
+ * taken, further keys are decompressed per call and counted as refused.
+ * A device on which the cache cannot be allocated goes on without one.
+ * TBLS_PK_CACHE=0 turns the cache off (TBLS_PK_LOOKUP=0 does too).
+ * tbls_pk_table_load and tbls_pk_table_clear leave the cache as it is: its
+ * rows depend on key bytes only; a key in both is taken from the table.
+ *
+ * tbls_pk_cache_stats: out[0] = keys taken from the cache, out[1] = keys
+ * learned, out[2] = valid keys a full cache refused, since the process began,
+ * the last tbls_pk_cache_clear or the last reset; out[3] = rows in use (not
+ * reset; a batch that holds a new key twice may leave a row unused).  Summed
+ * over the devices, each read under its lock after its stream is synchronised.
+ * tbls_pk_cache_clear forgets every learned key and zeroes the counters. */
+int tbls_pk_cache_stats(uint64_t out[4], int reset);
+int tbls_pk_cache_clear(void);
+
 /* A signature set whose keys are table indices (the unit of
  * BLS.prepareBatchVerify, BLS.java:353-368, with keys by validator index). */
 typedef struct {

@@ -611,6 +611,20 @@ class ValidatorKeyTable:
         return Committee(slot, indices)
 
 
+def pk_cache_stats(reset=False):
+    """(hits, learned, refused, rows_in_use) of the devices' learned key
+    caches (tbls_pk_cache_stats): byte keys a batch decompressed and found
+    valid are kept on the device, and later batches take them from there."""
+    out = (ctypes.c_uint64 * 4)()
+    native.check(native.lib().tbls_pk_cache_stats(out, 1 if reset else 0), "tbls_pk_cache_stats")
+    return tuple(int(x) for x in out)
+
+
+def pk_cache_clear():
+    """Forget every learned key on every device (tbls_pk_cache_clear)."""
+    native.check(native.lib().tbls_pk_cache_clear(), "tbls_pk_cache_clear")
+
+
 class Committee:
     """A resident sync committee (C ABI tbls_committee_load /
     tbls_fast_aggregate_verify_many_bits): the index list stays on the devices

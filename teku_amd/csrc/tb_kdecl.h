@@ -23,6 +23,7 @@
 #include <cstdlib>
 #include "tb_stages.h"
 #include "tb_fp12_wave.h"
+#include "tb_pkindex.h"  // pkx_cache, a parameter of the key index's kernels
 
 using namespace tb;
 
@@ -141,8 +142,9 @@ extern "C" __global__ void k_keys_coop(const uint8_t* __restrict__ pks, const ui
 extern "C" __global__ void k_sig_check_coop(const uint8_t* __restrict__ sigs, uint32_t n, g2a* __restrict__ sig_aff, uint8_t* __restrict__ sig_use, uint8_t* __restrict__ sig_code, uint32_t* __restrict__ n_bad);
 // the key table's index over its key bytes (k_pkindex.hip; workgroups of its TB_PKX_BLOCK threads)
 extern "C" __global__ void k_pkx_build(const uint32_t* __restrict__ keys, uint32_t K, uint32_t* slots, uint32_t mask, uint64_t seed);
-extern "C" __global__ void k_pk_lookup(const uint8_t* __restrict__ pks, uint32_t K, uint32_t align, const uint32_t* __restrict__ slots, uint32_t mask, uint64_t seed, const uint32_t* __restrict__ tab_keys, const g1a* __restrict__ tab_aff, const uint8_t* __restrict__ tab_code, g1a* __restrict__ pk_aff, uint8_t* __restrict__ pk_code, uint32_t* __restrict__ miss, unsigned long long* __restrict__ stat);
-extern "C" __global__ void k_pk_decompress_list(const uint8_t* __restrict__ pks, const uint32_t* __restrict__ list, g1a* __restrict__ pk_aff, uint8_t* __restrict__ pk_code);
+extern "C" __global__ void k_pk_lookup(const uint8_t* __restrict__ pks, uint32_t K, uint32_t align, const uint32_t* __restrict__ slots, uint32_t mask, uint64_t seed, const uint32_t* __restrict__ tab_keys, const g1a* __restrict__ tab_aff, const uint8_t* __restrict__ tab_code, pkx_cache cache, g1a* __restrict__ pk_aff, uint8_t* __restrict__ pk_code, uint32_t* __restrict__ miss, unsigned long long* __restrict__ stat);
+extern "C" __global__ void k_pk_decompress_list(const uint8_t* __restrict__ pks, const uint32_t* __restrict__ list, g1a* __restrict__ pk_aff, uint8_t* __restrict__ pk_code, uint32_t* __restrict__ seen);
+extern "C" __global__ void k_pk_learn(const uint8_t* __restrict__ pks, uint32_t align, const uint32_t* __restrict__ list, const g1a* __restrict__ pk_aff, const uint8_t* __restrict__ pk_code, pkx_cache cache);
 extern "C" __global__ void k_pk_resolve(const uint8_t* __restrict__ pks, uint32_t n, uint32_t align, const uint32_t* __restrict__ slots, uint32_t mask, uint64_t seed, const uint32_t* __restrict__ tab_keys, uint32_t* __restrict__ idx_out);
 // settling a failed batch (k_pair.hip; tb_lib.hip settle_sets)
 extern "C" __global__ void k_group_test_coop(const fp12* __restrict__ vals, uint32_t stride, uint32_t nseg, const uint32_t* __restrict__ list, uint8_t* __restrict__ out);

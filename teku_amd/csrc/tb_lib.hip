@@ -64,10 +64,11 @@ struct gbuf {
   gbuf(const gbuf&) = delete;
   gbuf& operator=(const gbuf&) = delete;
   ~gbuf() { release(); }
-  int ensure(size_t bytes) {
+  // exact: a buffer of a fixed size gets no headroom for growing
+  int ensure(size_t bytes, bool exact = false) {
     if (bytes <= cap) return 0;
     release();
-    const size_t nb = bytes < 4096 ? 4096 : bytes + bytes / 4;
+    const size_t nb = bytes < 4096 ? 4096 : exact ? bytes : bytes + bytes / 4;
     if ((HOST ? hipHostMalloc(&p, nb, hipHostMallocDefault) : hipMalloc(&p, nb)) != hipSuccess) {
       p = nullptr;
       return -1;
@@ -109,12 +110,35 @@ struct dev_ctx {
   dbuf tab_keys, pkx_slots, pkx_stat, pkx_miss;
   uint32_t pkx_cap = 0;
   uint64_t pkx_seed = 0;
+  // The learned key cache (tb_pkindex.h pkx_cache): byte keys
+  // that a key stage decompressed and found valid, kept with their points for
+  // the next batches' lookups.  pkc_rows: its fixed capacity (0: off --
+  // TBLS_PK_CACHE=0, TBLS_PK_LOOKUP=0 or TBLS_PK_CACHE_KEYS=0, read by
+  // tbls_init, which also draws pkc_seed).  pkc: allocated by the first key
+  // stage that looks up (pk_lookup_reserve) -- a head (PKC_HEAD bytes: the row
+  // counter, then at byte 8 the TB_PKC_STATS counters), the slots, the rows'
+  // keys, the rows' points.  Read and written by key stages only, between
+  // ws_acquire and ws_release like `ws`.
+  dbuf pkc;
+  uint32_t pkc_rows = 0;
+  uint64_t pkc_seed = 0;
+  // The miss count of the device's latest key stage that looked keys up, as
+  // far as it has arrived: k_pk_decompress_list stores its list's count into
+  // this pinned word (pk_seen_dev: the word's device address), and nothing
+  // waits for it.  pk_seen_K: the keys of the latest stage queued (0: none
+  // yet).  launch_partial predicts from the two whether the next batch's keys
+  // are known (pk_keys_known); a late or mismatched count only costs a stage
+  // order.
+  hbuf pk_seen;
+  uint32_t* pk_seen_dev = nullptr;
+  uint32_t pk_seen_K = 0;
   // resident committees (tbls_committee_load): per slot TB_CM_STRIDE bytes of
   // cmt (members, bad-member mask, valid-member row, the valid members' sum,
   // the load pass's code and failure count); size 0: empty slot
   dbuf cmt;
   uint32_t cm_size[TBLS_COMMITTEE_SLOTS] = {0, 0, 0, 0}, cm_sum_ok[TBLS_COMMITTEE_SLOTS] = {0, 0, 0, 0};
   hipEvent_t e_fork = nullptr, e_join[3] = {nullptr, nullptr, nullptr}, e_sig = nullptr;
+  hipEvent_t e_learn = nullptr;  // k_pk_learn has ended, on the key stream behind e_join[0] (launch_partial)
   hipEvent_t e_t0 = nullptr, e_t1 = nullptr;  // per-call device timing (shard_launch), created once
   // Last use of `ws` on any stream.  The device-resident API queues work on the
   // caller's stream and returns; every later user of `ws` (on whatever stream)
@@ -140,7 +164,7 @@ struct dev_ctx {
           ok(hipStreamCreateWithFlags(&aux[0], hipStreamNonBlocking)) && ok(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi)) &&
           ok(hipStreamCreateWithPriority(&aux[1], hipStreamNonBlocking, prio_hi)) &&
           ok(hipStreamCreateWithPriority(&aux[2], hipStreamNonBlocking, prio_hi)) && event(&e_join[2]) && event(&e_fork) && event(&e_join[0]) &&
-          event(&e_join[1]) && event(&e_sig) && event(&e_ws) && ok(hipEventCreate(&e_t0)) && ok(hipEventCreate(&e_t1)) &&
+          event(&e_join[1]) && event(&e_sig) && event(&e_learn) && event(&e_ws) && ok(hipEventCreate(&e_t0)) && ok(hipEventCreate(&e_t1)) &&
           !comb.ensure(TB_MSM_BUCKETS * sizeof(g1a))))
       return false;
     hipLaunchKernelGGL(k_g1_comb_init, dim3(TB_MSM_BUCKETS / TB_BLOCK), dim3(TB_BLOCK), 0, stream, comb.as<g1a>());
@@ -152,7 +176,7 @@ struct dev_ctx {
     (void)hipSetDevice(dev);
     for (hipStream_t s : {stream, aux[0], aux[1], aux[2]})
       if (s) (void)hipStreamDestroy(s);
-    for (hipEvent_t e : {e_fork, e_join[0], e_join[1], e_join[2], e_sig, e_t0, e_t1, e_ws})
+    for (hipEvent_t e : {e_fork, e_join[0], e_join[1], e_join[2], e_sig, e_learn, e_t0, e_t1, e_ws})
       if (e) (void)hipEventDestroy(e);
   }
 };
@@ -325,13 +349,42 @@ inline uint32_t pkx_align(const void* p) {
   return !(a & 15u) ? 16u : !(a & 3u) ? 4u : 1u;
 }
 
-// True when byte keys on c resolve from the table's index first.
-inline bool pk_lookup_on(const dev_ctx& c) { return c.tab_n && c.pkx_cap; }
+// True when byte keys on c resolve from the table's index.
+inline bool pk_table_index_on(const dev_ctx& c) { return c.tab_n && c.pkx_cap; }
+// True when byte keys on c are looked up before they are decompressed: in the
+// table's index, in the learned cache, or in both.
+inline bool pk_lookup_on(const dev_ctx& c) { return pk_table_index_on(c) || c.pkc_rows; }
 
-// Room for the miss list of a K-key stage; the caller holds the workspace
-// (ws_acquire) and `s` orders every earlier user of it, so growing drains s
-// first, as the workspace does.
+// The learned cache's buffer (dev_ctx::pkc) and the view its kernels take
+// (slots == nullptr: the device has no cache).
+#define PKC_HEAD 64u
+inline size_t pkc_zeroed_bytes(const dev_ctx& c) { return PKC_HEAD + (size_t)tb::pkx_capacity(c.pkc_rows) * 4; }  // the head and the slots
+inline tb::pkx_cache pk_cache_view(const dev_ctx& c) {
+  if (!c.pkc_rows || !c.pkc.p) return {nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 0};
+  const size_t o_keys = pkc_zeroed_bytes(c), o_points = o_keys + (size_t)c.pkc_rows * 48;
+  return {c.pkc.as<uint32_t>(PKC_HEAD), tb::pkx_capacity(c.pkc_rows) - 1u, c.pkc.as<uint32_t>(o_keys), c.pkc.as<uint32_t>(o_points), c.pkc_rows,
+          c.pkc.as<uint32_t>(0), c.pkc.as<unsigned long long>(8), c.pkc_seed};
+}
+
+// Room for the miss list of a K-key stage, and the learned cache on its first
+// use; the caller holds the workspace (ws_acquire) and `s` orders every
+// earlier user of it, so growing drains s first, as the workspace does.  A
+// cache that cannot be allocated is given up for the process (pkc_rows = 0):
+// the device goes on as without one, it does not fail its batches.
 int pk_lookup_reserve(dev_ctx& c, uint32_t K, hipStream_t s) {
+  if (!K) return TBLS_SUCCESS;
+  if (c.pkc_rows && !c.pkc.p) {  // an empty cache: the counters and every slot 0; the rows need no clearing
+    if (c.pk_seen.ensure(64) || hipHostGetDevicePointer((void**)&c.pk_seen_dev, c.pk_seen.p, 0) != hipSuccess ||
+        c.pkc.ensure(pkc_zeroed_bytes(c) + (size_t)c.pkc_rows * (48 + sizeof(g1a)), true)) {
+      (void)hipGetLastError();
+      c.pkc.release();
+      c.pkc_rows = 0;
+      c.pk_seen_dev = nullptr;
+    } else {
+      *c.pk_seen.as<uint32_t>() = 0xffffffffu;  // until the first count arrives: every key a miss
+      HIPCHK(hipMemsetAsync(c.pkc.p, 0, pkc_zeroed_bytes(c), s));
+    }
+  }
   const size_t need = ((size_t)K + 1) * 4;
   if (!pk_lookup_on(c) || need <= c.pkx_miss.cap) return TBLS_SUCCESS;
   HIPCHK(hipStreamSynchronize(s));
@@ -339,22 +392,34 @@ int pk_lookup_reserve(dev_ctx& c, uint32_t K, hipStream_t s) {
 }
 
 // The key stage of K byte keys: affine points and validity codes into pk_aff /
-// pk_code.  With a table index on the device (pk_lookup_on, pk_lookup_reserve
-// called) it is two steps: launch_pk_lookup -- k_pk_lookup copies the keys the
-// table knows and lists the others -- then k_pk_decompress_list decompresses
-// that list.  The same bytes give the same point and code either way, since
-// the table's entries came from k_pk_decompress.  Without an index:
-// k_pk_decompress over all K.  launch_byte_keys queues the whole stage on s;
-// looked_up: the caller has queued launch_pk_lookup already, on a stream s waits for.
+// pk_code.  With a lookup on the device (pk_lookup_on, pk_lookup_reserve
+// called) it is three steps: launch_pk_lookup -- k_pk_lookup copies the keys
+// that the table's index or the learned cache knows and lists the others --
+// then k_pk_decompress_list decompresses that list, and with a cache
+// launch_pk_learn -- k_pk_learn appends the list's valid keys to it.  The same
+// bytes give the same point and code either way, since the table's entries
+// came from k_pk_decompress and the cache's rows from k_pk_decompress_list.
+// Without a lookup: k_pk_decompress over all K.  launch_byte_keys queues the
+// stage on s; looked_up: the caller has queued launch_pk_lookup already, on a
+// stream s waits for; learn false: the caller queues launch_pk_learn itself,
+// behind the kernels that wait for the keys (launch_partial).
 int launch_pk_lookup(dev_ctx& c, hipStream_t s, const uint8_t* pks, uint32_t K, g1a* pk_aff, uint8_t* pk_code) {
   uint32_t* miss = c.pkx_miss.as<uint32_t>();
   HIPCHK(hipMemsetAsync(miss, 0, 4, s));
+  const bool tab = pk_table_index_on(c);
   hipLaunchKernelGGL(k_pk_lookup, dim3((K + TB_PKX_BLOCK - 1) / TB_PKX_BLOCK), dim3(TB_PKX_BLOCK), 0, s, pks, K, pkx_align(pks),
-                     c.pkx_slots.as<const uint32_t>(), c.pkx_cap - 1u, c.pkx_seed, c.tab_keys.as<const uint32_t>(), c.tab_aff.as<const g1a>(),
-                     c.tab_code.as<const uint8_t>(), pk_aff, pk_code, miss, c.pkx_stat.as<unsigned long long>());
+                     tab ? c.pkx_slots.as<const uint32_t>() : nullptr, tab ? c.pkx_cap - 1u : 0u, c.pkx_seed, c.tab_keys.as<const uint32_t>(),
+                     c.tab_aff.as<const g1a>(), c.tab_code.as<const uint8_t>(), pk_cache_view(c), pk_aff, pk_code, miss,
+                     c.pkx_stat.as<unsigned long long>());
   return TBLS_SUCCESS;
 }
-int launch_byte_keys(dev_ctx& c, hipStream_t s, const uint8_t* pks, uint32_t K, g1a* pk_aff, uint8_t* pk_code, bool looked_up = false) {
+void launch_pk_learn(dev_ctx& c, hipStream_t s, const uint8_t* pks, uint32_t K, const g1a* pk_aff, const uint8_t* pk_code) {
+  if (!K || !c.pkc_rows) return;
+  hipLaunchKernelGGL(k_pk_learn, dim3((K + TB_PKX_BLOCK - 1) / TB_PKX_BLOCK), dim3(TB_PKX_BLOCK), 0, s, pks, pkx_align(pks),
+                     c.pkx_miss.as<const uint32_t>(), pk_aff, pk_code, pk_cache_view(c));
+}
+int launch_byte_keys(dev_ctx& c, hipStream_t s, const uint8_t* pks, uint32_t K, g1a* pk_aff, uint8_t* pk_code, bool looked_up = false,
+                     bool learn = true) {
   if (!K) return TBLS_SUCCESS;
   const dim3 blk(TB_BLOCK), g((K + TB_BLOCK - 1) / TB_BLOCK);
   if (!pk_lookup_on(c)) {
@@ -363,9 +428,30 @@ int launch_byte_keys(dev_ctx& c, hipStream_t s, const uint8_t* pks, uint32_t K, 
   }
   if (!looked_up)
     if (const int rc = launch_pk_lookup(c, s, pks, K, pk_aff, pk_code)) return rc;
-  // the grid covers K: the list's length is only known on the device
-  hipLaunchKernelGGL(k_pk_decompress_list, g, blk, 0, s, pks, c.pkx_miss.as<const uint32_t>(), pk_aff, pk_code);
+  // the grids cover K: the list's length is only known on the device
+  hipLaunchKernelGGL(k_pk_decompress_list, g, blk, 0, s, pks, c.pkx_miss.as<const uint32_t>(), pk_aff, pk_code,
+                     c.pkc_rows ? c.pk_seen_dev : nullptr);
+  if (learn) launch_pk_learn(c, s, pks, K, pk_aff, pk_code);
+  if (c.pkc_rows) c.pk_seen_K = K;
   return TBLS_SUCCESS;
+}
+
+// The prediction that a batch's byte keys are in the learned cache (taken from
+// it, not decompressed): at most 1/8 of the latest key stage's keys were
+// misses.  Validator keys are a stable registry, so the last batch is the
+// best cheap predictor; below 1/8 the decompression beside the signature
+// checks is under 0.4 ms of the 3.2 ms it takes for a whole 131,072-key batch
+// (the shares in between are not measured).  Only with a cache: without one
+// the launches and their order are the parent's.  TB_PK_KNOWN_ORDER=0 builds
+// a library that never predicts, for the A/B of the two orders
+// (tools/build_variant.py).
+#ifndef TB_PK_KNOWN_ORDER
+#define TB_PK_KNOWN_ORDER 1
+#endif
+inline bool pk_keys_known(const dev_ctx& c) {
+  if (!TB_PK_KNOWN_ORDER || !c.pkc_rows || !c.pk_seen_K || !c.pk_seen.p) return false;
+  const uint32_t miss = *static_cast<const volatile uint32_t*>(c.pk_seen.p);
+  return (uint64_t)miss * 8 <= c.pk_seen_K;
 }
 
 // The Miller line kernel of a line group (tb_plan.h line_group): a lane quad,
@@ -384,7 +470,7 @@ struct partial_run {
   const key_src& keys;
   hipStream_t s, sa, sb, sh;  // the caller's, keys, signatures + bucket sums, hash
   bool late_join;             // bp.late_join with the streams side by side
-  // Byte keys on a device with a table index (pk_lookup_on): launch_partial
+  // Byte keys on a device that looks them up (pk_lookup_on): launch_partial
   // has queued the lookup on the caller's stream ahead of the fork, and the
   // key stream starts at the misses.
   bool pre_lookup;
@@ -454,7 +540,7 @@ struct partial_run {
       TB_EV(1, sa);
       TB_EV(2, sa);
     } else {
-      if (const int rc = launch_byte_keys(c, sa, b.pks, bp.n_keys, W.pk_aff, W.pk_code, pre_lookup)) return rc;
+      if (const int rc = launch_byte_keys(c, sa, b.pks, bp.n_keys, W.pk_aff, W.pk_code, pre_lookup, false)) return rc;  // learnt behind the join (launch_partial)
       TB_EV(1, sa);
       TB_EV(2, sa);
       launch_set_pk(sa, n, bp.w2, bp.multi, b.pk_off, keys, b.rand, set_P(), W.set_code, W.n_bad, W.mlist, W.mcnt, sig_P(), comb);
@@ -622,6 +708,8 @@ int launch_partial(dev_ctx& c, const tbls_dev_batch& b, hipStream_t s, void* par
   // bracket, for the exclusive stage times.
   const bool pre_lookup = bp.key == key_kind::decompress && bp.n_keys && pk_lookup_on(c) && !o.serial;
   const partial_run run{c, b, o, bp, W, keys, s, o.serial ? s : c.aux[0], o.serial ? s : c.aux[1], o.serial ? s : c.aux[2], late_join, pre_lookup};
+  // byte keys that are looked up, and the last key stage found (nearly) all of its own: no decompression to speak of in this batch
+  const bool keys_known = bp.key == key_kind::decompress && bp.n_keys && pk_keys_known(c);
   HIPCHK(hipMemsetAsync(W.set_code, 0, L.code_bytes, s));  // set_code and sig_code (adjacent; a grouped plan's pair codes after them)
   HIPCHK(hipMemsetAsync(W.n_bad, 0, 4, s));
   if (run.pre_lookup) {
@@ -638,6 +726,19 @@ int launch_partial(dev_ctx& c, const tbls_dev_batch& b, hipStream_t s, void* par
   HIPCHK(hipEventRecord(c.e_join[1], run.sb));
   if (const int rc = run.key_chain()) return rc;
   HIPCHK(hipEventRecord(c.e_join[0], run.sa));
+  // The cache learns behind the join: nothing in this batch reads what
+  // k_pk_learn writes, and a kernel of the key stream that is dispatched once
+  // the hash and signature kernels hold the chip ends only when a round of
+  // their waves has retired, however little it does.  Ahead of k_set_pk it
+  // held back the join: a 16,384-set tbls_batch_verify_each took 10.4 ms with
+  // every key cached and 11.0 ms with none, against 9.4-9.5 ms without a cache
+  // (DESIGN.md 3l).  The caller's stream waits for e_learn before ws_release,
+  // as for every stream: the kernel reads the workspace.
+  const bool learns = bp.key == key_kind::decompress && bp.n_keys && c.pkc_rows;
+  if (learns) {
+    launch_pk_learn(c, run.sa, b.pks, bp.n_keys, W.pk_aff, W.pk_code);
+    if (!o.serial) HIPCHK(hipEventRecord(c.e_learn, run.sa));
+  }
   // Bucket-sum batches with the key table: the hash waits for the signature
   // checks (sig_first).  Every large per-set kernel is one round of
   // register-full waves, so whichever starts first holds the whole chip until
@@ -646,8 +747,12 @@ int launch_partial(dev_ctx& c, const tbls_dev_batch& b, hipStream_t s, void* par
   // loops ended up after the line kernel, where the accumulator waited
   // ~1.4 ms for them with the chip nearly idle (rocprof trace of the 131k
   // step, profiles/r05_kernel_trace_step.txt).  With key decompression in
-  // the batch the hash-first order still measured faster.
-  if (late_join && bp.sig_first) HIPCHK(hipStreamWaitEvent(run.sh, c.e_sig, 0));
+  // the batch the hash-first order still measured faster -- so byte keys take
+  // the table's order only when the device is expected to know them
+  // (keys_known): 131k step with every key in the learned cache 32.69-32.93 ms
+  // hash first, 32.08-32.37 ms signature checks first
+  // (profiles/pk_learn.json).
+  if (late_join && (bp.sig_first || keys_known)) HIPCHK(hipStreamWaitEvent(run.sh, c.e_sig, 0));
   if (const int rc = run.hash_chain()) return rc;
   if (!o.serial) {
     HIPCHK(hipEventRecord(c.e_join[2], run.sh));
@@ -661,6 +766,7 @@ int launch_partial(dev_ctx& c, const tbls_dev_batch& b, hipStream_t s, void* par
   if (const int rc = run.miller()) return rc;
   if (late_join) HIPCHK(hipStreamWaitEvent(s, c.e_join[1], 0));  // every stream joins before ws_release
   if (o.settle) {
+    if (learns && !o.serial) HIPCHK(hipStreamWaitEvent(s, c.e_learn, 0));
     HIPCHK(hipGetLastError());
     HIPCHK(ws_release(c, s));
     return TBLS_SUCCESS;
@@ -668,6 +774,7 @@ int launch_partial(dev_ctx& c, const tbls_dev_batch& b, hipStream_t s, void* par
   TB_EV(11, s);
   if (const int rc = run.product_tree(partial_out)) return rc;
   HIPCHK(hipMemcpyAsync((uint8_t*)partial_out + sizeof(fp12), W.n_bad, 4, hipMemcpyDeviceToDevice, s));
+  if (learns && !o.serial) HIPCHK(hipStreamWaitEvent(s, c.e_learn, 0));
   HIPCHK(hipGetLastError());
   HIPCHK(ws_release(c, s));
   return TBLS_SUCCESS;
@@ -1357,16 +1464,24 @@ extern "C" int tbls_init(int n_devices, uint32_t flags) {
   }
   const int hw = count;
   g_pk_lookup = !(getenv("TBLS_PK_LOOKUP") && getenv("TBLS_PK_LOOKUP")[0] == '0');
+  // The learned key cache's rows per device: TBLS_PK_CACHE_KEYS (default
+  // 2,097,152: about 320 MB with the slots); none with TBLS_PK_CACHE=0 or
+  // without lookups.
+  uint32_t cache_rows = 2097152u;
+  if (const char* v = getenv("TBLS_PK_CACHE_KEYS")) cache_rows = (uint32_t)std::min<unsigned long long>(strtoull(v, nullptr, 10), 1ull << 28);
+  if (!g_pk_lookup || (getenv("TBLS_PK_CACHE") && getenv("TBLS_PK_CACHE")[0] == '0')) cache_rows = 0;
   if ((flags & TBLS_INIT_SHARE_DEVICES) && n_devices > 0 && n_devices <= 32)
     count = n_devices;  // contexts over the hardware devices round-robin
   else if (n_devices > 0 && n_devices < count)
     count = n_devices;
   for (int d = 0; d < count; d++) {
     dev_ctx* c = new dev_ctx();
-    if (!c->init(d % hw)) {
+    // the cache's hash seed: from the OS entropy source, as the table index's
+    if (!c->init(d % hw) || (cache_rows && fill_random(&c->pkc_seed, 1))) {
       delete c;
       break;
     }
+    c->pkc_rows = cache_rows;
     g_ctx.push_back(c);
   }
   (void)hipGetLastError();  // a context that failed to set up leaves no sticky error for later calls' checks
@@ -1565,7 +1680,7 @@ extern "C" int tbls_pk_table_resolve(const uint8_t* pks, size_t n, uint32_t* idx
   if (n && (!pks || !idx_out)) return TBLS_BAD_ARGUMENT;
   if (n > 0xffffffffu / 48) return TBLS_BAD_ARGUMENT;
   return with_device([&](dev_ctx& c) -> int {
-    if (!pk_lookup_on(c)) return (int)TBLS_BAD_ARGUMENT;  // no table (or no index: TBLS_PK_LOOKUP=0)
+    if (!pk_table_index_on(c)) return (int)TBLS_BAD_ARGUMENT;  // no table (or no index: TBLS_PK_LOOKUP=0)
     if (!n) return (int)TBLS_SUCCESS;
     const size_t o_idx = align_up(n * 48);
     if (c.in.ensure(o_idx + n * 4)) return (int)TBLS_DEVICE_ERROR;
@@ -1591,6 +1706,38 @@ extern "C" int tbls_pk_lookup_stats(uint64_t out[2], int reset) {
     HIPCHK(hipStreamSynchronize(c->stream));
     out[0] += v[0];
     out[1] += v[1];
+    return TBLS_SUCCESS;
+  });
+}
+
+// The learned key caches' counters, summed over the devices: lookups' hits,
+// rows learned, keys refused by a full cache, rows in use.
+extern "C" int tbls_pk_cache_stats(uint64_t out[4], int reset) {
+  const caller_device keep;
+  if (!out) return TBLS_BAD_ARGUMENT;
+  out[0] = out[1] = out[2] = out[3] = 0;
+  if (ensure_init()) return TBLS_DEVICE_ERROR;
+  return each_device(true, false, [&](dev_ctx* c) -> int {  // key stages queued on a caller's stream count too
+    if (!c->pkc_rows || !c->pkc.p) return TBLS_SUCCESS;
+    uint64_t v[1 + tb::TB_PKC_STATS] = {0, 0, 0, 0};  // the head: the row counter (a 32-bit word), the counters
+    HIPCHK(hipMemcpyAsync(v, c->pkc.p, sizeof v, hipMemcpyDeviceToHost, c->stream));
+    if (reset) HIPCHK(hipMemsetAsync(c->pkc.as<uint8_t>(8), 0, 8 * tb::TB_PKC_STATS, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < tb::TB_PKC_STATS; i++) out[i] += v[1 + i];
+    out[3] += std::min<uint64_t>(v[0] & 0xffffffffu, c->pkc_rows);  // appenders racing for the last rows overshoot the counter
+    return TBLS_SUCCESS;
+  });
+}
+
+// Forget every learned key on every device (the counters too); the buffers stay.
+extern "C" int tbls_pk_cache_clear(void) {
+  const caller_device keep;
+  if (ensure_init()) return TBLS_DEVICE_ERROR;
+  return each_device(true, true, [&](dev_ctx* c) -> int {  // the last key stage has finished
+    if (!c->pkc_rows || !c->pkc.p) return TBLS_SUCCESS;
+    HIPCHK(hipMemsetAsync(c->pkc.p, 0, pkc_zeroed_bytes(*c), c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->pk_seen_K = 0;  // and nothing is expected of the next batch's keys (pk_keys_known)
     return TBLS_SUCCESS;
   });
 }

@@ -143,4 +143,137 @@ TB_HD TB_INLINE uint32_t pkx_insert(uint32_t* slots, uint32_t mask, const uint32
   return TB_PKX_MISS;
 }
 
+// ---------------------------------------------------------------------------
+// The learned key cache: an index of the same kind that grows
+// while batches run.  A row is a key's 48 bytes and the 96-byte affine point
+// the key stage computed from them; rows are only ever appended, and a slot is
+// published after its row, so a reader that sees a slot sees its row.
+//
+//  * an appender probes like a lookup; at the first empty slot it reserves a
+//    row (one atomic add on the row counter), writes the row, makes it visible
+//    (pkx_release) and publishes the slot with a compare-and-swap.  When the
+//    swap loses to another key it keeps its row and probes on; when it loses to
+//    equal bytes (two sets of one batch carry the same key) it stops: the
+//    bytes have one findable entry and the reserved row stays unused;
+//  * an appender that reads a slot another appender of the same launch
+//    published reads the row behind an acquire (pkx_acquire); lookups run in
+//    later launches and need none;
+//  * when no row is left the key is refused (TB_PKX_FULL) and counted: nothing
+//    is evicted; `rows` is fixed and `mask + 1` is pkx_capacity(rows), so the
+//    load factor stays at most 1/2.
+//
+// tests/native/pkcache_check.cpp runs these on the CPU.
+#define TB_PKX_POINT_WORDS 24u   // a 96-byte affine point
+#define TB_PKX_DUP 0xfffffffeu   // pkx_append: equal bytes are in the cache already
+#define TB_PKX_FULL 0xfffffffdu  // pkx_append: no row left
+enum { TB_PKC_HITS = 0, TB_PKC_LEARNED = 1, TB_PKC_REFUSED = 2, TB_PKC_STATS = 3 };  // pkx_cache::stat
+
+struct pkx_cache {
+  uint32_t* slots;  // mask + 1 of them (nullptr: no cache)
+  uint32_t mask;
+  uint32_t* keys;    // rows x 12 words
+  uint32_t* points;  // rows x 24 words
+  uint32_t rows;
+  uint32_t* n_rows;  // rows reserved; concurrent appenders may push it a little past `rows`
+  unsigned long long* stat;  // TB_PKC_*: lookups' hits, rows published, keys refused for want of a row
+  uint64_t seed;
+};
+
+TB_HD TB_INLINE uint32_t pkx_word_load(const uint32_t* p) {
+#if TB_DEVICE_PASS
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+  return *p;
+#endif
+}
+
+// Between the row's stores and the slot's compare-and-swap: the stores reach
+// memory every compute die reads (an agent-scope release; the explicit wait
+// keeps the swap behind the write-back).
+TB_HD TB_INLINE void pkx_release() {
+#if TB_DEVICE_PASS
+  __threadfence();
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+}
+
+// Between reading a slot and reading its row within one launch: drops this
+// compute unit's cached lines (an agent-scope acquire).
+TB_HD TB_INLINE void pkx_acquire() {
+#if TB_DEVICE_PASS
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+#endif
+}
+
+TB_HD TB_INLINE void pkx_count(unsigned long long* p) {
+#if TB_DEVICE_PASS
+  atomicAdd(p, 1ull);
+#else
+  ++*p;
+#endif
+}
+
+// A free row's index, or TB_PKX_MISS when every row is taken.
+TB_HD TB_INLINE uint32_t pkx_reserve(const pkx_cache& c) {
+  if (pkx_word_load(c.n_rows) >= c.rows) return TB_PKX_MISS;  // a full cache's counter stops growing
+#if TB_DEVICE_PASS
+  const uint32_t r = atomicAdd(c.n_rows, 1u);
+#else
+  const uint32_t r = (*c.n_rows)++;
+#endif
+  return r < c.rows ? r : TB_PKX_MISS;
+}
+
+// Append the key q with its point pt.  Returns the row it published;
+// TB_PKX_DUP when equal bytes are in the cache (before, or by a concurrent
+// appender); TB_PKX_FULL when no row is left; TB_PKX_MISS when no slot was
+// free within the probe bound.
+TB_HD TB_INLINE uint32_t pkx_append(const pkx_cache& c, const uint32_t q[TB_PKX_WORDS], const uint32_t pt[TB_PKX_POINT_WORDS]) {
+  uint32_t s = pkx_first(pkx_hash(q, c.seed), c.mask);
+  const uint32_t bound = pkx_probe_bound(c.mask + 1u);
+  uint32_t row = TB_PKX_MISS;
+  for (uint32_t p = 0; p < bound; p++, s = pkx_next(s, c.mask)) {
+    uint32_t v = pkx_word_load(c.slots + s);
+    if (v == 0) {
+      if (row == TB_PKX_MISS) {
+        row = pkx_reserve(c);
+        if (row == TB_PKX_MISS) {
+          pkx_count(c.stat + TB_PKC_REFUSED);
+          return TB_PKX_FULL;
+        }
+        uint32_t* k = c.keys + (size_t)row * TB_PKX_WORDS;
+        uint32_t* a = c.points + (size_t)row * TB_PKX_POINT_WORDS;
+        TB_UNROLL for (uint32_t i = 0; i < TB_PKX_WORDS; i++) k[i] = q[i];
+        TB_UNROLL for (uint32_t i = 0; i < TB_PKX_POINT_WORDS; i++) a[i] = pt[i];
+        pkx_release();
+      }
+      v = pkx_cas(c.slots + s, 0u, row + 1u);
+      if (v == 0) {
+        pkx_count(c.stat + TB_PKC_LEARNED);
+        return row;
+      }
+    }
+    pkx_acquire();
+    if (pkx_equal(c.keys + (size_t)(v - 1u) * TB_PKX_WORDS, q)) return TB_PKX_DUP;
+  }
+  return TB_PKX_MISS;
+}
+
+// The key stage's lookup of the key q: the loaded table's index first
+// (t_slots, nullptr: no table), then the cache (c.slots, nullptr: none).
+#define TB_PKX_SRC_NONE 0u
+#define TB_PKX_SRC_TABLE 1u
+#define TB_PKX_SRC_CACHE 2u
+struct pkx_hit {
+  uint32_t src, idx;  // TB_PKX_SRC_*; the table index or the cache row (TB_PKX_MISS with TB_PKX_SRC_NONE)
+};
+TB_HD TB_INLINE pkx_hit pkx_find_two(const uint32_t* t_slots, uint32_t t_mask, const uint32_t* t_keys, uint64_t t_seed, const pkx_cache& c,
+                                     const uint32_t q[TB_PKX_WORDS]) {
+  uint32_t i = t_slots ? pkx_find(t_slots, t_mask, t_keys, q, t_seed) : TB_PKX_MISS;
+  if (i != TB_PKX_MISS) return {TB_PKX_SRC_TABLE, i};
+  i = c.slots ? pkx_find(c.slots, c.mask, c.keys, q, c.seed) : TB_PKX_MISS;
+  if (i != TB_PKX_MISS) return {TB_PKX_SRC_CACHE, i};
+  return {TB_PKX_SRC_NONE, TB_PKX_MISS};
+}
+
 }  // namespace tb

@@ -159,6 +159,8 @@ _SIGS = {
     "tbls_pk_table_clear": (ctypes.c_int, []),
     "tbls_pk_table_resolve": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32)]),
     "tbls_pk_lookup_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
+    "tbls_pk_cache_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
+    "tbls_pk_cache_clear": (ctypes.c_int, []),
     "tbls_batch_verify_idx": (
         ctypes.c_int,
         [
