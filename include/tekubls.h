@@ -229,6 +229,48 @@ int tbls_pk_lookup_stats(uint64_t out[2], int reset);
 int tbls_pk_cache_stats(uint64_t out[4], int reset);
 int tbls_pk_cache_clear(void);
 
+/* ---- hash-point memo ----
+ * The service verifies gossip in batches of a few hundred sets whose signing
+ * roots repeat from batch to batch: every attester of a committee signs the
+ * same AttestationData, and a failed batch is verified again in halves
+ * (AggregatingSignatureVerificationService.java:187-227).  H(m) =
+ * hash_to_G2(m, DST) depends on the message bytes and the fixed Ethereum DST
+ * alone (HashToCurve.java:24-31), so each device can keep the points it has
+ * computed: a resident array of rows, each an affine G2 point with its skip
+ * byte, and on the host an index from message bytes to rows.  With the memo
+ * on, the host entries tbls_batch_verify*, tbls_batch_verify_each* (their
+ * _idx and _grouped forms, and the settling of a failed batch included),
+ * tbls_verify_each and tbls_fast_aggregate_verify_many* resolve every
+ * set's message before they stage a shard, hash only the messages that are
+ * neither resident nor repeated inside the shard, and give every pair its
+ * point with one copy kernel.  A point from a row is the 192 bytes the same
+ * kernels wrote for the same message, so every verdict is bit for bit what it
+ * is without the memo.
+ *
+ * Messages of more than 64 bytes are hashed every time and never resident
+ * (Teku's signing roots are 32 bytes).  When a shard brings more new messages
+ * than there are free rows, the device's whole memo is flushed and refilled
+ * from that shard.  A shard of more than 16,384 sets bypasses the memo: there
+ * the host-side resolving costs more than any measured gain.
+ * Calls with a DST of their own (tbls_verify,
+ * tbls_aggregate_verify, tbls_sign*, tbls_hash_to_g2) and the
+ * device-resident entries tbls_dev_batch_partial* never touch the memo.
+ *
+ * tbls_msg_memo_configure: rows per device, capped at 1,048,576 (about 200 MB
+ * per device, allocated by the first batch that resolves); 0 turns the memo
+ * off.  Forgets everything learned and zeroes the counters; takes effect for
+ * batches staged afterwards.  TBLS_MSG_MEMO=rows in the environment, read by
+ * tbls_init, does the same; the memo is off by default.  A device on which
+ * the rows cannot be allocated goes on without a memo.
+ * tbls_msg_memo_stats: out[0] = pairs whose point came from a row learned by
+ * an earlier call, out[1] = messages hashed, out[2] = flushes, since the last
+ * configure or reset; out[3] = rows in use (not reset).  Summed over the
+ * devices, each read under its lock.
+ * tbls_msg_memo_clear forgets every learned point; the counters stay. */
+int tbls_msg_memo_configure(uint32_t rows);
+int tbls_msg_memo_stats(uint64_t out[4], int reset);
+int tbls_msg_memo_clear(void);
+
 /* A signature set whose keys are table indices (the unit of
  * BLS.prepareBatchVerify, BLS.java:353-368, with keys by validator index). */
 typedef struct {

@@ -23,6 +23,35 @@ public final class HipBatchVerifier {
   }
 
   /*
+   * The library's hash-point memo (tbls_msg_memo_configure): rows per device,
+   * 0 turns it off.  Gossip batches repeat a slot's signing roots
+   * (AggregatingSignatureVerificationService.java:187-227); with the memo every
+   * batch staged afterwards hashes only the messages whose H(m) no earlier
+   * batch left on the device.  Verdicts are unchanged.  Process state.
+   */
+  public static void configureHashMemo(final int rows) {
+    if (!HipLoader.INSTANCE.isPresent()) {
+      return;
+    }
+    final int rc = TekuBlsHipMemo.msgMemoConfigure(Math.min(Math.max(rows, 0), TekuBlsHipMemo.MAX_ROWS));
+    if (rc != 0) {
+      throw new BlsException("tbls_msg_memo_configure failed: " + rc);
+    }
+  }
+
+  /* {pairs whose H(m) came from a row, messages hashed, flushes, rows in use} (tbls_msg_memo_stats) */
+  public static long[] hashMemoStats(final boolean reset) {
+    final int[] words = new int[8];
+    final int rc = TekuBlsHipMemo.msgMemoStats(words, reset);
+    if (rc != 0) {
+      throw new BlsException("tbls_msg_memo_stats failed: " + rc);
+    }
+    return new long[] {
+      TekuBlsHipMemo.stat(words, 0), TekuBlsHipMemo.stat(words, 1), TekuBlsHipMemo.stat(words, 2), TekuBlsHipMemo.stat(words, 3)
+    };
+  }
+
+  /*
    * BLS.batchVerify(keys, messages, signatures) over all sets as one
    * randomized device batch (BLS.java:230-336); when it fails, okPerSet[i] =
    * BLS.fastAggregateVerify(set i) (BLS.java:185-207), settled on the devices

@@ -25,6 +25,10 @@
  *     one call, tbls_batch_verify_each_grouped -- a grouped batch that fails
  *     settles its per-set verdicts from the grouped pass's own work, with no
  *     second staging, decoding or hashing of the sets.
+ *  6. hashMemoRows (opt-in, 0 by default): doStart configures the library's
+ *     hash-point memo (tbls_msg_memo_configure), so a slot's signing roots,
+ *     which gossip delivers over many batches (the reference's l.187-227), are
+ *     hashed once per device and copied from its rows afterwards.
  * Python mirror and tests: teku_amd/service.py, tests/test_service.py
  * (placement simulated over 8 devices), tests/test_gpu_configs.py.
  */
@@ -63,6 +67,7 @@ public class HipAggregatingSignatureVerificationService extends SignatureVerific
   private final int maxBatchSize;
   private final boolean groupMessages;
   private final boolean groupSettle;
+  private final int hashMemoRows;
   private final BlockingQueue<Task> queue;
   private final AsyncRunner asyncRunner;
   private final Counter batchCounter;
@@ -97,6 +102,20 @@ public class HipAggregatingSignatureVerificationService extends SignatureVerific
       final int maxBatchSize,
       final boolean groupMessages,
       final boolean groupSettle) {
+    this(metricsSystem, asyncRunnerFactory, completionRunner, queueCapacity, maxBatchSize, groupMessages,
+        groupSettle, 0);
+  }
+
+  public HipAggregatingSignatureVerificationService(
+      final MetricsSystem metricsSystem,
+      final AsyncRunnerFactory asyncRunnerFactory,
+      final AsyncRunner completionRunner,
+      final int queueCapacity,
+      final int maxBatchSize,
+      final boolean groupMessages,
+      final boolean groupSettle,
+      final int hashMemoRows) {
+    this.hashMemoRows = hashMemoRows;
     this.groupMessages = groupMessages;
     this.groupSettle = groupSettle;
     this.numThreads = HipBatchVerifier.deviceCount();
@@ -131,6 +150,9 @@ public class HipAggregatingSignatureVerificationService extends SignatureVerific
 
   @Override
   protected SafeFuture<?> doStart() {
+    if (hashMemoRows > 0) {
+      HipBatchVerifier.configureHashMemo(hashMemoRows);
+    }
     for (int i = 0; i < numThreads; i++) {
       asyncRunner
           .runAsync(this::run)

@@ -625,6 +625,28 @@ def pk_cache_clear():
     native.check(native.lib().tbls_pk_cache_clear(), "tbls_pk_cache_clear")
 
 
+def msg_memo_configure(rows):
+    """Rows per device of the hash-point memo (tbls_msg_memo_configure; 0:
+    off): batches staged afterwards hash only the messages whose H(m) no
+    earlier batch left on the device.  Forgets everything learned."""
+    if not 0 <= rows < 2**32:
+        raise ValueError("rows out of range")
+    native.check(native.lib().tbls_msg_memo_configure(rows), "tbls_msg_memo_configure")
+
+
+def msg_memo_stats(reset=False):
+    """(pairs_from_rows, messages_hashed, flushes, rows_in_use) of the
+    devices' hash-point memos (tbls_msg_memo_stats)."""
+    out = (ctypes.c_uint64 * 4)()
+    native.check(native.lib().tbls_msg_memo_stats(out, 1 if reset else 0), "tbls_msg_memo_stats")
+    return tuple(int(x) for x in out)
+
+
+def msg_memo_clear():
+    """Forget every learned hash point on every device (tbls_msg_memo_clear)."""
+    native.check(native.lib().tbls_msg_memo_clear(), "tbls_msg_memo_clear")
+
+
 class Committee:
     """A resident sync committee (C ABI tbls_committee_load /
     tbls_fast_aggregate_verify_many_bits): the index list stays on the devices

@@ -146,6 +146,14 @@ extern "C" __global__ void k_pk_lookup(const uint8_t* __restrict__ pks, uint32_t
 extern "C" __global__ void k_pk_decompress_list(const uint8_t* __restrict__ pks, const uint32_t* __restrict__ list, g1a* __restrict__ pk_aff, uint8_t* __restrict__ pk_code, uint32_t* __restrict__ seen);
 extern "C" __global__ void k_pk_learn(const uint8_t* __restrict__ pks, uint32_t align, const uint32_t* __restrict__ list, const g1a* __restrict__ pk_aff, const uint8_t* __restrict__ pk_code, pkx_cache cache);
 extern "C" __global__ void k_pk_resolve(const uint8_t* __restrict__ pks, uint32_t n, uint32_t align, const uint32_t* __restrict__ slots, uint32_t mask, uint64_t seed, const uint32_t* __restrict__ tab_keys, uint32_t* __restrict__ idx_out);
+// the hash-point memo (k_msgmemo.hip; workgroups of TB_MEMO_BLOCK threads, TB_MEMO_CHUNKS threads per point): the words of
+// src and learn as tb_msgmemo.h spells them (pinned by static_assert in tb_lib.hip)
+#define TB_MEMO_BLOCK 256u
+#define TB_MEMO_CHUNKS 12u
+#define TB_MEMO_SRC_ROW 0x80000000u
+#define TB_MEMO_NONE 0xffffffffu
+extern "C" __global__ void k_memo_fill(const uint32_t* __restrict__ src, const uint32_t* __restrict__ set_grp, uint32_t n_pairs, const g2a* __restrict__ Qh, const uint8_t* __restrict__ skiph, const g2a* __restrict__ rows, const uint8_t* __restrict__ row_skip, g2a* __restrict__ Q, uint8_t* __restrict__ skip);
+extern "C" __global__ void k_memo_learn(const uint32_t* __restrict__ learn, uint32_t m_hash, const g2a* __restrict__ Qh, const uint8_t* __restrict__ skiph, g2a* __restrict__ rows, uint8_t* __restrict__ row_skip);
 // settling a failed batch (k_pair.hip; tb_lib.hip settle_sets)
 extern "C" __global__ void k_group_test_coop(const fp12* __restrict__ vals, uint32_t stride, uint32_t nseg, const uint32_t* __restrict__ list, uint8_t* __restrict__ out);
 extern "C" __global__ void k_settle_mask(const uint8_t* __restrict__ set_code, uint32_t n, uint8_t* __restrict__ skip);

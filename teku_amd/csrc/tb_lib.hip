@@ -28,10 +28,12 @@
 #include "tb_settle.h"  // the group-test descent of settling a failed batch
 #include "tb_pack.h"  // the staging image of a host batch: set kinds, layout, fill
 #include "tb_group.h"  // the sets of a batch grouped by message, and the grouped staging image
+#include "tb_msgmemo.h"  // the hash-point memo: the host index over a device's resident rows, and the image's regions of a launch that resolved
 
 static_assert(TB_PARTIAL_BYTES == TBLS_PARTIAL_BYTES, "partial record size");
 static_assert(tb::plan::LINE_BYTES_PER_PAIR == TB_LINE_BYTES_PER_PAIR, "tb_plan.h: line bytes per pair");
 static_assert(tb::plan::HROW_SET_BYTES == sizeof(tb::hrow_set), "tb_plan.h: row-hash workspace per set");
+static_assert(tb::memo::SRC_ROW == TB_MEMO_SRC_ROW && tb::memo::LEARN_NONE == TB_MEMO_NONE, "tb_msgmemo.h: the words k_msgmemo.hip reads");
 
 using tb::caller_device;
 using namespace tb::plan;
@@ -139,6 +141,16 @@ struct dev_ctx {
   uint32_t cm_size[TBLS_COMMITTEE_SLOTS] = {0, 0, 0, 0}, cm_sum_ok[TBLS_COMMITTEE_SLOTS] = {0, 0, 0, 0};
   hipEvent_t e_fork = nullptr, e_join[3] = {nullptr, nullptr, nullptr}, e_sig = nullptr;
   hipEvent_t e_learn = nullptr;  // k_pk_learn has ended, on the key stream behind e_join[0] (launch_partial)
+  // The hash-point memo (tb_msgmemo.h): the host index, read and
+  // written under `mu` only, and the rows it speaks of -- memo.rows affine G2
+  // points, then (at a multiple of 256 bytes) their skip bytes -- allocated by
+  // the first shard that resolves (memo_reserve).  The rows are read by
+  // k_memo_fill and written by k_memo_learn only, between ws_acquire and
+  // ws_release like `ws`.  e_mlearn: k_memo_learn has ended, on the hash
+  // stream behind e_join[2] (launch_partial).
+  tb::memo::index memo;
+  dbuf memo_rows;
+  hipEvent_t e_mlearn = nullptr;
   hipEvent_t e_t0 = nullptr, e_t1 = nullptr;  // per-call device timing (shard_launch), created once
   // Last use of `ws` on any stream.  The device-resident API queues work on the
   // caller's stream and returns; every later user of `ws` (on whatever stream)
@@ -164,7 +176,7 @@ struct dev_ctx {
           ok(hipStreamCreateWithFlags(&aux[0], hipStreamNonBlocking)) && ok(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi)) &&
           ok(hipStreamCreateWithPriority(&aux[1], hipStreamNonBlocking, prio_hi)) &&
           ok(hipStreamCreateWithPriority(&aux[2], hipStreamNonBlocking, prio_hi)) && event(&e_join[2]) && event(&e_fork) && event(&e_join[0]) &&
-          event(&e_join[1]) && event(&e_sig) && event(&e_learn) && event(&e_ws) && ok(hipEventCreate(&e_t0)) && ok(hipEventCreate(&e_t1)) &&
+          event(&e_join[1]) && event(&e_sig) && event(&e_learn) && event(&e_mlearn) && event(&e_ws) && ok(hipEventCreate(&e_t0)) && ok(hipEventCreate(&e_t1)) &&
           !comb.ensure(TB_MSM_BUCKETS * sizeof(g1a))))
       return false;
     hipLaunchKernelGGL(k_g1_comb_init, dim3(TB_MSM_BUCKETS / TB_BLOCK), dim3(TB_BLOCK), 0, stream, comb.as<g1a>());
@@ -176,7 +188,7 @@ struct dev_ctx {
     (void)hipSetDevice(dev);
     for (hipStream_t s : {stream, aux[0], aux[1], aux[2]})
       if (s) (void)hipStreamDestroy(s);
-    for (hipEvent_t e : {e_fork, e_join[0], e_join[1], e_join[2], e_sig, e_learn, e_t0, e_t1, e_ws})
+    for (hipEvent_t e : {e_fork, e_join[0], e_join[1], e_join[2], e_sig, e_learn, e_mlearn, e_t0, e_t1, e_ws})
       if (e) (void)hipEventDestroy(e);
   }
 };
@@ -255,13 +267,21 @@ struct partial_opts {
   // n_msgs distinct messages, and the CSR (device memory) lists each one's sets.
   uint32_t n_msgs = 0;
   const uint32_t *grp_off = nullptr, *grp_sets = nullptr;
+  // A launch that resolved its messages against the device's hash-point memo
+  // (shard_launch, run_each): b.msgs / b.msg_off hold the m_hash messages left
+  // to hash; src (a word per distinct message), learn (a word per hashed
+  // message) and, for an ungrouped pass, set_grp (a word per set) are device
+  // memory (tb_msgmemo.h).
+  bool memo = false;
+  uint32_t m_hash = 0;
+  const uint32_t *memo_src = nullptr, *memo_learn = nullptr, *memo_setgrp = nullptr;
 };
 
 // The regions of a ws_layout as typed pointers into the workspace at w.
 struct ws_ptrs {
   g1a *pk_aff, *P, *set_P, *grp_part;
-  g2a *Q, *sig_aff;
-  uint8_t *pk_code, *skip, *set_code, *sig_code, *sig_use, *pair_code, *grp_pskip;
+  g2a *Q, *sig_aff, *Qh;
+  uint8_t *pk_code, *skip, *set_code, *sig_code, *sig_use, *pair_code, *grp_pskip, *skiph;
   uint32_t *msm_cnt, *msm_off, *msm_cur, *msm_idx, *mlist, *mcnt, *n_bad, *grp_item;
   g2j* msm_sum;
   hrow_set* hrow;
@@ -275,7 +295,10 @@ struct ws_ptrs {
         mlist((uint32_t*)(w + L.mlist)), mcnt((uint32_t*)(w + L.mcnt)), n_bad((uint32_t*)(w + L.n_bad)), grp_item((uint32_t*)(w + L.grp_item)),
         msm_sum((g2j*)(w + L.msm_sum)),
         hrow((hrow_set*)(w + L.hrow)), lines((uint4*)(w + L.lines)), f((fp12*)(w + L.f)), fpart((fp12*)(w + L.fpart)),
-        fpart2((fp12*)(w + L.fpart2)), segv((fp12*)(w + L.segv)) {}
+        fpart2((fp12*)(w + L.fpart2)), segv((fp12*)(w + L.segv)) {
+    Qh = (g2a*)(w + L.Qh);
+    skiph = w + L.skiph;
+  }
 };
 
 // The affine keys a stage reads, with their validity codes: the call's own
@@ -454,6 +477,13 @@ inline bool pk_keys_known(const dev_ctx& c) {
   return (uint64_t)miss * 8 <= c.pk_seen_K;
 }
 
+// The memo's kernels: TB_MEMO_CHUNKS threads per point; the rows' skip bytes
+// follow the memo.rows points of dev_ctx::memo_rows.
+inline dim3 memo_grid(uint32_t points) { return dim3((uint32_t)(((uint64_t)points * TB_MEMO_CHUNKS + TB_MEMO_BLOCK - 1) / TB_MEMO_BLOCK)); }
+inline size_t memo_skip_off(uint32_t rows) { return align_up((size_t)rows * sizeof(g2a)); }
+inline uint8_t* memo_row_skip(const dev_ctx& c) { return c.memo_rows.as<uint8_t>(memo_skip_off(c.memo.rows)); }
+static_assert(sizeof(g2a) % 16 == 0, "the rows are copied as 16-byte words: hipMalloc's base and every row are 16-byte aligned");
+
 // The Miller line kernel of a line group (tb_plan.h line_group): a lane quad,
 // a lane pair or one lane per pair.
 inline auto line_kernel_of(int lg) { return lg == 4 ? k_miller_lines_quad : lg == 2 ? k_miller_lines_duo : k_miller_lines_w2; }
@@ -570,9 +600,15 @@ struct partial_run {
   // priority its waves are dispatched first and the shorter key / signature
   // stages fill the SIMDs around them, instead of its last waves running
   // alone after the others finish.
+  // With the memo (bp.memo) the kernels hash the bp.n_hash messages the host
+  // left into Qh / skiph, and k_memo_fill then gives every main pair its Q
+  // and skip byte from there or from the device's rows: with nothing left to
+  // hash it is the only kernel on this stream.
   int hash_chain() const {
-    g2a* Q = W.Q;
-    uint8_t* skip = W.skip;
+    g2a* Q = bp.memo ? W.Qh : W.Q;
+    uint8_t* skip = bp.memo ? W.skiph : W.skip;
+    const uint32_t nh = bp.n_hash;
+    const dim3 gh((nh + TB_BLOCK - 1) / TB_BLOCK);  // one thread per message to hash
     TB_EV(6, sh);
     switch (bp.hash) {
       case hash_kind::none:
@@ -609,8 +645,16 @@ struct partial_run {
     }
     if (bp.hash == hash_kind::quad || bp.hash == hash_kind::duo || bp.hash == hash_kind::w2)  // the exact formulas for the sets it flags (skip == 2)
       hipLaunchKernelGGL(k_set_hash_fix, gh, blk, 0, sh, b.msgs, b.msg_off, o.dst, o.dlen, nh, Q, skip);
+    if (bp.memo && bp.pp.n_msgs)
+      hipLaunchKernelGGL(k_memo_fill, memo_grid(bp.pp.n_msgs), dim3(TB_MEMO_BLOCK), 0, sh, o.memo_src, o.memo_setgrp, bp.pp.n_msgs,
+                         (const g2a*)W.Qh, (const uint8_t*)W.skiph, c.memo_rows.as<const g2a>(), memo_row_skip(c), W.Q, W.skip);
     TB_EV(7, sh);
     return TBLS_SUCCESS;
+  }
+  // the rows learn the hashed messages the host gave a row (launch_partial queues it behind the join)
+  void memo_learn() const {
+    hipLaunchKernelGGL(k_memo_learn, memo_grid(bp.n_hash), dim3(TB_MEMO_BLOCK), 0, sh, o.memo_learn, bp.n_hash, (const g2a*)W.Qh,
+                       (const uint8_t*)W.skiph, c.memo_rows.as<g2a>(), memo_row_skip(c));
   }
 
   // --- Miller loops of all pairs (pairs of invalid sets contribute 1) ---------
@@ -675,7 +719,7 @@ struct partial_run {
 
 int launch_partial(dev_ctx& c, const tbls_dev_batch& b, hipStream_t s, void* partial_out, ws_layout& L, const partial_opts& o) {
   const batch_plan bp(b.n, b.n_keys, o.cm ? key_source::bits : o.key_idx ? key_source::table : key_source::bytes, o.settle, plan_env::get(),
-                      o.grp_off && o.grp_sets ? o.n_msgs : 0u);
+                      o.grp_off && o.grp_sets ? o.n_msgs : 0u, o.memo ? o.m_hash : HASH_ALL);
   L = ws_layout(bp);
   tb::stat_add(tb::TB_STAT_PARTIALS);
   HIPCHK(ws_acquire(c, s));
@@ -758,6 +802,17 @@ int launch_partial(dev_ctx& c, const tbls_dev_batch& b, hipStream_t s, void* par
     HIPCHK(hipEventRecord(c.e_join[2], run.sh));
     HIPCHK(hipStreamWaitEvent(s, c.e_join[2], 0));
   }
+  // The memo's rows learn behind the join, as the key cache does and for the
+  // same reason: nothing in this batch reads what k_memo_learn writes.  The
+  // caller's stream waits for e_mlearn before ws_release, so the rows of this
+  // batch are complete before the next batch's k_memo_fill (which starts
+  // behind ws_acquire), and a flush in the next batch -- whose learn kernel
+  // overwrites rows -- cannot overtake this batch's fill.
+  const bool mlearns = bp.memo && bp.n_hash;
+  if (mlearns) {
+    run.memo_learn();
+    if (!o.serial) HIPCHK(hipEventRecord(c.e_mlearn, run.sh));
+  }
   HIPCHK(hipStreamWaitEvent(s, c.e_join[0], 0));
   if (!late_join)
     HIPCHK(hipStreamWaitEvent(s, c.e_join[1], 0));
@@ -767,6 +822,7 @@ int launch_partial(dev_ctx& c, const tbls_dev_batch& b, hipStream_t s, void* par
   if (late_join) HIPCHK(hipStreamWaitEvent(s, c.e_join[1], 0));  // every stream joins before ws_release
   if (o.settle) {
     if (learns && !o.serial) HIPCHK(hipStreamWaitEvent(s, c.e_learn, 0));
+    if (mlearns && !o.serial) HIPCHK(hipStreamWaitEvent(s, c.e_mlearn, 0));
     HIPCHK(hipGetLastError());
     HIPCHK(ws_release(c, s));
     return TBLS_SUCCESS;
@@ -775,6 +831,7 @@ int launch_partial(dev_ctx& c, const tbls_dev_batch& b, hipStream_t s, void* par
   if (const int rc = run.product_tree(partial_out)) return rc;
   HIPCHK(hipMemcpyAsync((uint8_t*)partial_out + sizeof(fp12), W.n_bad, 4, hipMemcpyDeviceToDevice, s));
   if (learns && !o.serial) HIPCHK(hipStreamWaitEvent(s, c.e_learn, 0));
+  if (mlearns && !o.serial) HIPCHK(hipStreamWaitEvent(s, c.e_mlearn, 0));
   HIPCHK(hipGetLastError());
   HIPCHK(ws_release(c, s));
   return TBLS_SUCCESS;
@@ -841,7 +898,25 @@ struct shard_opts {
   uint32_t dlen = 43;
   bool settle = false;  // the settle layout (partial_opts::settle): no partial record
   group_mode gm = GROUP_OFF;
+  // The batch entries (their DST is ETH2_DST, which the memo is keyed for):
+  // resolve the shard's messages against the device's hash-point memo when it
+  // is on.  Calls with a DST of their own leave it false.
+  bool memo = false;
 };
+
+// The memo's rows on c for a shard about to resolve (lock held): allocated on
+// first use; true when the device has a memo.  A device where the allocation
+// fails goes on without one (memo.rows = 0), as with the key cache.
+bool memo_reserve(dev_ctx& c) {
+  if (!c.memo.rows) return false;
+  if (c.memo_rows.p) return true;
+  if (c.memo_rows.ensure(memo_skip_off(c.memo.rows) + c.memo.rows, true)) {
+    (void)hipGetLastError();
+    c.memo.configure(0);
+    return false;
+  }
+  return true;
+}
 // What shard_launch leaves behind: the workspace layout of the pipeline that
 // ran, the partial record (device memory, the shard's c->in) and the sets
 // staged; when the grouped plan ran, its messages and the byte offsets of the
@@ -858,8 +933,25 @@ struct shard_run {
 // Stage sets[lo, hi) on device c (its lock held) and queue the partial
 // pipeline on c->stream, filling R: the 580-byte partial record lands at
 // R.dpart -- nothing is synchronized.  e_t0/e_t1 bracket the kernels.
+// With so.memo on a device that has a memo, the shard's messages are first
+// resolved against its index (tb_msgmemo.h): the image then carries only the
+// messages left to hash, with src, learn and -- for an ungrouped pass --
+// set_grp in regions after the usual ones.
+template <class SET>
+int shard_launch_resolved(dev_ctx* c, const SET* sets, size_t lo, size_t hi, const uint64_t* rand, const shard_opts& so, shard_run& R,
+                          bool& resolved);
+// A shard that resolved and then failed invalidates the index: the rows it
+// promised may never have been written.
 template <class SET>
 int shard_launch(dev_ctx* c, const SET* sets, size_t lo, size_t hi, const uint64_t* rand, const shard_opts& so, shard_run& R) {
+  bool resolved = false;
+  const int rc = shard_launch_resolved(c, sets, lo, hi, rand, so, R, resolved);
+  if (rc && resolved) c->memo.invalidate();
+  return rc;
+}
+template <class SET>
+int shard_launch_resolved(dev_ctx* c, const SET* sets, size_t lo, size_t hi, const uint64_t* rand, const shard_opts& so, shard_run& R,
+                          bool& resolved) {
   constexpr bool idx_mode = !std::is_same<SET, tbls_set>::value;  // keys from the table: indices, or committee bit rows
   constexpr bool bits_mode = std::is_same<SET, set_bits_i>::value;
   R = shard_run();
@@ -870,15 +962,21 @@ int shard_launch(dev_ctx* c, const SET* sets, size_t lo, size_t hi, const uint64
     if (hi > lo) cm = committee_src(*c, sets[lo].slot);
   groups G;
   bool grouped = false;
-  if (so.gm != GROUP_OFF && !so.settle && !bits_mode) {
-    G = group_messages(sets, lo, hi);
-    grouped = group_pays((uint32_t)(hi - lo), G.m, so.gm == GROUP_FORCE);
+  const bool group_try = so.gm != GROUP_OFF && !so.settle && !bits_mode;
+  const bool use_memo = so.memo && hi > lo && hi - lo <= TB_MEMO_SETS_MAX && memo_reserve(*c);
+  if (group_try || use_memo) G = group_messages(sets, lo, hi);
+  if (group_try) grouped = group_pays((uint32_t)(hi - lo), G.m, so.gm == GROUP_FORCE);
+  tb::memo::resolved MR;
+  if (use_memo) {
+    MR = c->memo.resolve(G, !grouped);
+    resolved = true;
   }
-  packed_grouped p;
+  tb::memo::packed_memo p;
   if (grouped)
-    p = pack_layout_grouped(sets, lo, hi, so.dlen, G);
+    static_cast<packed_grouped&>(p) = pack_layout_grouped(sets, lo, hi, so.dlen, G);
   else
     static_cast<packed&>(p) = pack_layout(sets, lo, hi, so.dlen);
+  if (use_memo) p = tb::memo::pack_layout_memo(p, grouped, G, MR);
   const size_t in_total = p.total + TBLS_PARTIAL_BYTES + 256;
   hipStream_t s = c->stream;
   if (in_total > c->in.cap || in_total > c->hin.cap) HIPCHK(hipStreamSynchronize(s));  // buffers may still be read
@@ -887,6 +985,7 @@ int shard_launch(dev_ctx* c, const SET* sets, size_t lo, size_t hi, const uint64
     pack_fill_grouped(c->hin.as<uint8_t>(), p, sets, lo, rand, so.dst, so.dlen, G);
   else
     pack_fill(c->hin.as<uint8_t>(), p, sets, lo, rand, so.dst, so.dlen);
+  if (use_memo) tb::memo::pack_fill_memo(c->hin.as<uint8_t>(), p, G, MR);
   HIPCHK(hipMemcpyAsync(c->in.p, c->hin.p, p.total, hipMemcpyHostToDevice, s));
   uint8_t* di = c->in.as<uint8_t>();
   tbls_dev_batch b;
@@ -913,6 +1012,15 @@ int shard_launch(dev_ctx* c, const SET* sets, size_t lo, size_t hi, const uint64
     R.in_grpoff = p.off_grpoff;
     R.in_grpsets = p.off_grpsets;
     R.in_rand = p.off_rand;
+  }
+  if (use_memo) {
+    b.msgs = di + p.off_hmsgs;
+    b.msg_off = (const uint32_t*)(di + p.off_hmsgoff);
+    o.memo = true;
+    o.m_hash = p.m_hash;
+    o.memo_src = (const uint32_t*)(di + p.off_src);
+    o.memo_learn = (const uint32_t*)(di + p.off_learn);
+    o.memo_setgrp = grouped ? nullptr : (const uint32_t*)(di + p.off_setgrp);
   }
   if (const int rc = launch_partial(*c, b, s, R.dpart, R.L, o)) return rc;
   HIPCHK(hipEventRecord(c->e_t1, s));
@@ -1108,6 +1216,7 @@ static int settle_range(dev_ctx* c, const SET* sets, size_t lo, size_t hi, const
   if (settle_ready(ran.n)) return settle_sets(c, ran, ok);
   shard_opts so;
   so.settle = true;
+  so.memo = true;  // the second staging of a failed batch finds its messages resident
   for (size_t a = lo; a < hi; a += TB_SETTLE_MAX) {
     const size_t b = std::min(hi, a + (size_t)TB_SETTLE_MAX);
     shard_run R;
@@ -1309,6 +1418,7 @@ struct batch_pass {
     runs.resize(G);
     shard_opts so;
     so.gm = gm;
+    so.memo = true;
     std::vector<int> rcs(G, 0);
     for_each_shard(G, [&](int g) { rcs[g] = shard_launch(ctx(g), sets, pl.cut[g], pl.cut[g + 1], rand, so, runs[g]); });
     for (int g = 0; g < G; g++)
@@ -1482,6 +1592,8 @@ extern "C" int tbls_init(int n_devices, uint32_t flags) {
       break;
     }
     c->pkc_rows = cache_rows;
+    // the hash-point memo's rows per device: TBLS_MSG_MEMO (default 0: off)
+    if (const char* v = getenv("TBLS_MSG_MEMO")) c->memo.configure((uint32_t)std::min<unsigned long long>(strtoull(v, nullptr, 10), TB_MEMO_ROWS_MAX));
     g_ctx.push_back(c);
   }
   (void)hipGetLastError();  // a context that failed to set up leaves no sticky error for later calls' checks
@@ -1742,6 +1854,49 @@ extern "C" int tbls_pk_cache_clear(void) {
   });
 }
 
+// --------------------------------------------------------------------------
+// the hash-point memo (tb_msgmemo.h)
+// --------------------------------------------------------------------------
+// Rows per device (0: off), for batches staged afterwards; everything learned
+// is forgotten and the row buffers are dropped (the next shard that resolves
+// allocates its device's anew).
+extern "C" int tbls_msg_memo_configure(uint32_t rows) {
+  const caller_device keep;
+  if (ensure_init()) return TBLS_DEVICE_ERROR;
+  return each_device(true, true, [&](dev_ctx* c) -> int {  // the rows' last readers have finished
+    c->memo.configure(rows);
+    c->memo_rows.release();
+    return TBLS_SUCCESS;
+  });
+}
+
+// Pairs served from a row learned by an earlier call, messages hashed,
+// flushes, rows in use (not reset), summed over the devices.
+extern "C" int tbls_msg_memo_stats(uint64_t out[4], int reset) {
+  const caller_device keep;
+  if (!out) return TBLS_BAD_ARGUMENT;
+  out[0] = out[1] = out[2] = out[3] = 0;
+  if (ensure_init()) return TBLS_DEVICE_ERROR;
+  return each_device(false, false, [&](dev_ctx* c) -> int {  // the index is host state under the device's lock
+    out[0] += c->memo.hits;
+    out[1] += c->memo.hashed;
+    out[2] += c->memo.flushes;
+    out[3] += c->memo.used;
+    if (reset) c->memo.reset_counters();
+    return TBLS_SUCCESS;
+  });
+}
+
+// Forget every learned hash point on every device; the buffers and the counters stay.
+extern "C" int tbls_msg_memo_clear(void) {
+  const caller_device keep;
+  if (ensure_init()) return TBLS_DEVICE_ERROR;
+  return each_device(false, false, [&](dev_ctx* c) -> int {  // rows are reassigned only by kernels queued behind ws_acquire
+    c->memo.invalidate();
+    return TBLS_SUCCESS;
+  });
+}
+
 extern "C" size_t tbls_pk_table_size(void) {
   if (ensure_init()) return 0;
   dev_ctx* c = ctx_for(0);
@@ -1784,18 +1939,42 @@ extern "C" int tbls_verify(const uint8_t pk[48], const uint8_t* msg, size_t len,
 // pass (k_each.hip): shared per-set stages with r = 1, then one thread per set
 // for its two-pair Miller loop and final exponentiation.
 // Keys as bytes (decompressed here), table indices or committee bit rows.
+// With a hash-point memo on the device the messages are resolved as
+// shard_launch resolves them (one pair per set): the messages left are hashed
+// into Qh / skiph behind the pass's workspace, k_memo_fill gives every set its
+// Q, and k_memo_learn follows, all on the one stream.
+template <class SET>
+static int run_each_resolved(dev_ctx* c, const SET* sets, size_t lo, size_t hi, uint8_t* ok_host, bool& resolved);
 template <class SET>
 static int run_each(int d, const SET* sets, size_t lo, size_t hi, uint8_t* ok_host) {
-  constexpr bool bytes_mode = std::is_same<SET, tbls_set>::value, bits_mode = std::is_same<SET, set_bits_i>::value;
   dev_ctx* c = ctx_for(d);
   if (!c) return TBLS_DEVICE_ERROR;
   std::lock_guard<std::mutex> lk(c->mu);
+  bool resolved = false;
+  const int rc = run_each_resolved(c, sets, lo, hi, ok_host, resolved);
+  if (rc && resolved) c->memo.invalidate();  // the rows it promised may never have been written
+  return rc;
+}
+template <class SET>
+static int run_each_resolved(dev_ctx* c, const SET* sets, size_t lo, size_t hi, uint8_t* ok_host, bool& resolved) {
+  constexpr bool bytes_mode = std::is_same<SET, tbls_set>::value, bits_mode = std::is_same<SET, set_bits_i>::value;
   tb::stat_add(tb::TB_STAT_EACH);
   HIPCHK(hipSetDevice(c->dev));
   if (const int rc = check_keys(c, sets, lo, hi)) return rc;
-  packed p = pack_layout(sets, lo, hi, 43);
+  tb::memo::packed_memo p;
+  static_cast<packed&>(p) = pack_layout(sets, lo, hi, 43);
+  const bool use_memo = hi > lo && hi - lo <= TB_MEMO_SETS_MAX && memo_reserve(*c);
+  groups G;
+  tb::memo::resolved MR;
+  if (use_memo) {
+    G = group_messages(sets, lo, hi);
+    MR = c->memo.resolve(G, true);
+    resolved = true;
+    p = tb::memo::pack_layout_memo(p, false, G, MR);
+  }
   if (c->hin.ensure(p.total + 256) || c->in.ensure(p.total + 256)) return TBLS_DEVICE_ERROR;
   pack_fill(c->hin.as<uint8_t>(), p, sets, lo, nullptr, ETH2_DST, 43);  // r = 1 for every set
+  if (use_memo) tb::memo::pack_fill_memo(c->hin.as<uint8_t>(), p, G, MR);
   hipStream_t s = c->stream;
   HIPCHK(ws_acquire(*c, s));
   HIPCHK(hipStreamSynchronize(s));  // ws may be reallocated below
@@ -1803,7 +1982,9 @@ static int run_each(int d, const SET* sets, size_t lo, size_t hi, uint8_t* ok_ho
   const uint8_t* di = c->in.as<uint8_t>();
   const uint32_t n = p.n, K = bytes_mode ? p.K : 0u;  // keys to decompress
   const each_layout E(n, K);
-  if (c->ws.ensure(E.total)) return TBLS_DEVICE_ERROR;
+  const uint32_t m_hash = use_memo ? p.m_hash : 0u;
+  const size_t o_qh = E.total, o_skiph = o_qh + align_up((size_t)m_hash * sizeof(g2a));  // the hashed points, behind the pass's regions
+  if (c->ws.ensure(o_skiph + align_up(m_hash))) return TBLS_DEVICE_ERROR;
   if (const int rc = pk_lookup_reserve(*c, K, s)) return rc;
   uint8_t* w = c->ws.as<uint8_t>();
   g1a* P = (g1a*)(w + E.P);
@@ -1824,7 +2005,20 @@ static int run_each(int d, const SET* sets, size_t lo, size_t hi, uint8_t* ok_ho
                   nullptr, nullptr);
   }
   hipLaunchKernelGGL(k_sig_check, g, blk, 0, s, di + p.off_sigs, n, sig_aff, sig_use, sig_code, n_bad, 0u);
-  hipLaunchKernelGGL(k_set_hash, g, blk, 0, s, di + p.off_msgs, (const uint32_t*)(di + p.off_msgoff), di + p.off_dst, 43u, n, Q, skip);
+  if (!use_memo) {
+    hipLaunchKernelGGL(k_set_hash, g, blk, 0, s, di + p.off_msgs, (const uint32_t*)(di + p.off_msgoff), di + p.off_dst, 43u, n, Q, skip);
+  } else {
+    g2a* Qh = (g2a*)(w + o_qh);
+    uint8_t* skiph = w + o_skiph;
+    if (m_hash)
+      hipLaunchKernelGGL(k_set_hash, dim3((m_hash + TB_BLOCK - 1) / TB_BLOCK), blk, 0, s, di + p.off_hmsgs, (const uint32_t*)(di + p.off_hmsgoff),
+                         di + p.off_dst, 43u, m_hash, Qh, skiph);
+    hipLaunchKernelGGL(k_memo_fill, memo_grid(n), dim3(TB_MEMO_BLOCK), 0, s, (const uint32_t*)(di + p.off_src), (const uint32_t*)(di + p.off_setgrp),
+                       n, (const g2a*)Qh, (const uint8_t*)skiph, c->memo_rows.as<const g2a>(), memo_row_skip(*c), Q, skip);
+    if (m_hash)
+      hipLaunchKernelGGL(k_memo_learn, memo_grid(m_hash), dim3(TB_MEMO_BLOCK), 0, s, (const uint32_t*)(di + p.off_learn), m_hash, (const g2a*)Qh,
+                         (const uint8_t*)skiph, c->memo_rows.as<g2a>(), memo_row_skip(*c));
+  }
   hipLaunchKernelGGL(k_verify_each, g, blk, 0, s, (const g1a*)P, (const g2a*)Q, (const uint8_t*)skip, (const uint8_t*)set_code,
                      (const g2a*)sig_aff, (const uint8_t*)sig_use, (const uint8_t*)sig_code, n, okd);
   HIPCHK(hipGetLastError());

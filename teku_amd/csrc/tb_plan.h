@@ -479,9 +479,19 @@ struct prod_level {
   prod_dst dst;
 };
 
+constexpr uint32_t HASH_ALL = 0xffffffffu;  // batch_plan's m_hash without a memo: every main pair's message is hashed
+
 struct batch_plan {
   pair_plan pp;
   uint32_t n_keys;  // keys to decompress (0 with a table source)
+  // The messages to hash.  Without the hash-point memo (tb_msgmemo.h) these
+  // are the main pairs' messages, pp.n_msgs, hashed straight into Q.  With it
+  // (memo): the messages the host found neither resident nor repeated, hashed
+  // into Qh / skiph (ws_layout), from where k_memo_fill gives every main pair
+  // its Q.  The hash kernel, the row-hash workspace and the w2 kernel's park
+  // area follow this count, not pp.n_msgs.
+  uint32_t n_hash;
+  bool memo;
   hash_kind hash = hash_kind::none;
   sig_kind sig;
   key_kind key;
@@ -516,12 +526,15 @@ struct batch_plan {
   // group, the wave / split choice, the accumulator plan and the product
   // levels follow from n_msgs messages and n_msgs + 64 pairs; the per-set
   // kernels (key stage, signature check, w2) from n.
+  // m_hash (HASH_ALL: no memo): the messages to hash of a launch that resolved.
   batch_plan(uint32_t n, uint32_t n_keys_in, key_source src, bool settle = false, const plan_env& env = plan_env::get(),
-             uint32_t n_msgs = 0)
+             uint32_t n_msgs = 0, uint32_t m_hash = HASH_ALL)
       : pp(n, settle, env, n_msgs), n_keys(src == key_source::bytes ? n_keys_in : 0u) {
     const bool small = n <= TB_HASH_WAVE_MAX && env.coop;
     w2 = use_w2(n, env);
-    const uint32_t nh = pp.n_msgs;  // messages to hash
+    memo = m_hash != HASH_ALL;
+    n_hash = memo ? std::min(m_hash, pp.n_msgs) : pp.n_msgs;
+    const uint32_t nh = n_hash;  // messages to hash
     if (!nh) hash = hash_kind::none;
     else if (nh <= TB_HASH_WAVE_MAX) hash = env.coop ? hash_kind::coop : hash_kind::wave;
     else if (nh <= env.row_max) hash = hash_kind::row;
@@ -584,6 +597,10 @@ struct ws_layout {
   // grp_part, grp_pskip: k_group_pk_sum_coop's first item per group and the
   // items' partial sums with their infinity flags.
   size_t pair_code, set_P, grp_item, grp_part, grp_pskip;
+  // Memo plans only (empty otherwise, after every other region, so that no
+  // offset moves without a memo): the n_hash hashed points and their skip
+  // bytes, which k_memo_fill and k_memo_learn copy as 16-byte words.
+  size_t Qh, skiph;
   size_t code_bytes;  // set_code .. the end of the last code row: zeroed by every launch
   uint32_t nb_f;
   // A function of the plan alone: what a host launch knows beyond it (where
@@ -619,7 +636,7 @@ struct ws_layout {
     msm_sum = o;  o = align_up(o + (msm ? (size_t)TB_MSM_BUCKETS * sizeof(g2j) : 0));
     mlist = o;    o = align_up(o + (size_t)n * 4);
     mcnt = o;     o = align_up(o + 4);
-    const uint32_t nh = pp.n_msgs;
+    const uint32_t nh = bp.n_hash;
     hrow = o;     o = align_up(o + (bp.hash == hash_kind::row ? (size_t)nh * HROW_SET_BYTES : 0));
     // the line buffer; before the line kernel runs, k_set_hash_w2 parks the
     // chains' affine addends in it (a g2a per set)
@@ -635,6 +652,10 @@ struct ws_layout {
     grp_item = o;  o = align_up(o + (grouped ? ((size_t)pp.n_msgs + 1) * 4 : 0));
     grp_part = o;  o = align_up(o + (size_t)ni * sizeof(g1a));
     grp_pskip = o; o = align_up(o + ni);
+    const size_t nq = bp.memo ? bp.n_hash : 0;
+    Qh = o;        o = align_up(o + nq * sizeof(g2a));
+    skiph = o;     o = align_up(o + nq);
+    static_assert(sizeof(g2a) % 16 == 0, "k_memo_fill copies points as 16-byte words: Q, Qh (multiples of 256) and every entry are 16-byte aligned");
     total = o;
   }
 };

@@ -47,6 +47,14 @@ tbls_batch_verify_each_grouped: a grouped batch that fails settles its per-set
 verdicts from the grouped pass's own work, with no second staging, decoding or
 hashing of the sets.
 
+Hash-point memo (`hash_memo_rows=N`, off by default): gossip delivers a slot's
+attestations over seconds, in batches of a few hundred sets that sign the same
+few signing roots, so batch after batch would hash the same 32 bytes again.
+With N > 0 start() configures the library's per-device memo of N rows
+(tbls_msg_memo_configure): every later batch, its settling included, hashes
+only the messages no earlier batch left on the device.  Verdicts are
+unchanged; metrics() reports the memo's counters.
+
 Semantics kept from the reference: a full queue completes the future
 exceptionally with ServiceCapacityExceededException (verify, l.143-152);
 verify() before start() raises (assertIsRunning); a one-task failed batch is
@@ -239,6 +247,7 @@ class AggregatingSignatureVerificationService:
         batch_grouped_fn: Optional[Callable] = None,
         group_settle: bool = False,
         batch_each_grouped_fn: Optional[Callable] = None,
+        hash_memo_rows: int = 0,
     ):
         """num_threads: workers (default: one per device for the device
         backend, 1 for a custom batch_fn).  batch_each_fn(sets, n_gpus,
@@ -252,7 +261,9 @@ class AggregatingSignatureVerificationService:
         (with group_messages): the batch is one call of
         batch_each_grouped_fn(sets, n_gpus, timing) -> (ok, per-set verdicts)
         (tbls_batch_verify_each_grouped), which settles a failed grouped
-        batch from the grouped pass."""
+        batch from the grouped pass.  hash_memo_rows: rows per device of the
+        library's hash-point memo, configured by start() when not 0 (process
+        state: it stays configured for every caller of the library)."""
         if num_threads is None:
             num_threads = default_num_threads() if batch_fn is None else 1
         self.num_threads = max(1, num_threads)
@@ -267,6 +278,7 @@ class AggregatingSignatureVerificationService:
             batch_grouped_fn = (lambda sets, n_gpus, timing: _hip_batch_grouped(sets, n_gpus, timing, True)) if group_force else _hip_batch_grouped
         self._batch_grouped_fn = batch_grouped_fn
         self.group_settle = group_settle
+        self.hash_memo_rows = int(hash_memo_rows)
         if batch_each_grouped_fn is None:
             batch_each_grouped_fn = ((lambda sets, n_gpus, timing: _hip_batch_each_grouped(sets, n_gpus, timing, True)) if group_force
                                      else _hip_batch_each_grouped)
@@ -295,6 +307,10 @@ class AggregatingSignatureVerificationService:
 
     # -- Service lifecycle -------------------------------------------------
     def start(self):
+        if self.hash_memo_rows:
+            from . import bls
+
+            bls.msg_memo_configure(self.hash_memo_rows)
         self._running = True
         for i in range(self.num_threads):
             t = threading.Thread(target=self._run, name=f"sigverify-{i}", daemon=True)
@@ -453,7 +469,13 @@ class AggregatingSignatureVerificationService:
         _batch_size histogram) and the device's: sets verified per second of
         kernel time (summed over devices) and of host wall time, the last
         batch's timing."""
+        memo = {}
+        if self.hash_memo_rows:  # (pairs from rows, messages hashed, flushes, rows in use), process-wide
+            from . import bls
+
+            memo = {"hash_memo": bls.msg_memo_stats()}
         return {
+            **memo,
             "signature_verifications_queue_size": self.queue_size(),
             "signature_verifications_batch_count_total": self.batch_count,
             "signature_verifications_task_count_total": self.task_count,
