@@ -229,6 +229,32 @@ int tbls_pk_lookup_stats(uint64_t out[2], int reset);
 int tbls_pk_cache_stats(uint64_t out[4], int reset);
 int tbls_pk_cache_clear(void);
 
+/* ---- per-key comb rows ----
+ * For every key it keeps -- a row of the learned cache, a key of the loaded
+ * table -- the device also keeps 15 affine multiples of the key (a 4-tooth
+ * fixed-base comb, 1,440 bytes), computed once: by the batch that learns the
+ * key, or by tbls_pk_table_load.  A single-key set of a large batch (one that
+ * runs the two-wave key kernel: 32,768 sets or more per device, in the batch
+ * entries and in tbls_verify_each alike; TBLS_W2_MIN, read once per process,
+ * moves that threshold for all two-wave kernels and is meant for tests and
+ * tuning) whose key has such a row takes [r] pk from it in 15
+ * doublings and at most 16 additions instead of 62 and about 24 plus a
+ * per-call table; the point is the same, so every result is bit for bit what
+ * it is without the rows.  A batch never reads a row it builds itself.
+ *
+ * TBLS_PK_COMB=0 (read by tbls_init) turns the rows off.  TBLS_PK_COMB_KEYS
+ * caps the cache's comb rows per device (default: every cache row; 3.0 GB at
+ * 2,097,152 rows): cache rows beyond the cap never get one and are multiplied
+ * as before.  A device on which a region cannot be allocated goes on without
+ * it.  tbls_pk_cache_clear forgets the cache's comb rows with its keys;
+ * tbls_pk_table_load and tbls_pk_table_clear rebuild and drop the table's.
+ *
+ * tbls_pk_comb_stats: out[0] = sets whose [r] pk came from a comb row, out[1]
+ * = rows built for learned keys, out[2] = rows built for table keys, since the
+ * process began or the last reset; out[3] = the caches' comb-row capacity (0:
+ * none).  Summed over the devices as tbls_pk_cache_stats is. */
+int tbls_pk_comb_stats(uint64_t out[4], int reset);
+
 /* ---- hash-point memo ----
  * The service verifies gossip in batches of a few hundred sets whose signing
  * roots repeat from batch to batch: every attester of a committee signs the

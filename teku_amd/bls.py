@@ -625,6 +625,14 @@ def pk_cache_clear():
     native.check(native.lib().tbls_pk_cache_clear(), "tbls_pk_cache_clear")
 
 
+def pk_comb_stats(reset=False):
+    """(sets_served, cache_rows_built, table_rows_built, cache_comb_capacity)
+    of the devices' per-key comb rows (tbls_pk_comb_stats)."""
+    out = (ctypes.c_uint64 * 4)()
+    native.check(native.lib().tbls_pk_comb_stats(out, 1 if reset else 0), "tbls_pk_comb_stats")
+    return tuple(int(x) for x in out)
+
+
 def msg_memo_configure(rows):
     """Rows per device of the hash-point memo (tbls_msg_memo_configure; 0:
     off): batches staged afterwards hash only the messages whose H(m) no

@@ -1,6 +1,7 @@
 // k_set_pk at two waves per SIMD (see k_w2_hash.hip for why a translation unit
 // of its own): per set, aggregate key and P = [r] apk (affine).
 #include "tb_kbody.h"
+#include "tb_pkcomb.h"
 
 using namespace tb;
 
@@ -61,6 +62,62 @@ extern "C" __global__ void __launch_bounds__(TB_BLOCK, 2)
     code = TB_PK_IS_INFINITY;
   else if (!jac_to_aff(out, mul_u64_aff_w2_lds(pk_aff[k], r, &tab[threadIdx.x])))
     code = TB_PK_IS_INFINITY;
+  P[i] = out;
+  if (code != TB_SUCCESS) {
+    set_code[i] = (uint8_t)code;
+    atomicAdd(n_bad, 1u);
+  }
+}
+
+// k_set_pk_w2 for a device that keeps comb rows (tb_pkcomb.h):
+// a single-key set whose key has a complete row takes [r] pk from it -- 15
+// doublings and at most 16 mixed additions, no table to build -- and every
+// other lane runs exactly what k_set_pk_w2 runs.  Which row: by index
+// (key_idx) the table region's row key_idx itself, when the device has that
+// region (tab_comb) -- every table key whose code is TB_SUCCESS has a row --
+// else the key's reference word pk_ref[k] from k_pk_lookup_ref (the table
+// region's row or the learned cache's, cache_comb; TB_PKREF_READY only when
+// that row was complete before this batch began).  The same codes and n_bad as
+// stage_set_pk.  comb_stat[0] += the sets multiplied through a row, one atomic
+// per wave.
+extern "C" __global__ void __launch_bounds__(TB_BLOCK, 2)
+    k_set_pk_comb_w2(const uint32_t* __restrict__ pk_off, const g1a* __restrict__ pk_aff, const uint8_t* __restrict__ pk_code,
+                     const uint64_t* __restrict__ rand, uint32_t n, g1a* __restrict__ P, uint8_t* __restrict__ set_code,
+                     uint32_t* __restrict__ n_bad, const uint32_t* __restrict__ key_idx, uint32_t tab_n, uint32_t multi_wave,
+                     g1a* __restrict__ P2, const g1a* __restrict__ comb, const uint32_t* __restrict__ pk_ref,
+                     const g1a* __restrict__ cache_comb, const g1a* __restrict__ tab_comb, unsigned long long* __restrict__ comb_stat) {
+  __shared__ g1a tab[3 * TB_BLOCK];  // the window path's table, as k_set_pk_w2's
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t b = pk_off[i], e = pk_off[i + 1];
+  if (e - b != 1 || (multi_wave & 4u)) {
+    set_pk_body(i, pk_off, pk_aff, pk_code, rand, P, set_code, n_bad, key_idx, tab_n, multi_wave, P2, comb);
+    return;
+  }
+  const uint64_t r = rand[i];
+  if (P2) P2[i] = neg_r_g1(comb, r);
+  g1a out;
+  out.x = fp_zero();
+  out.y = fp_zero();
+  int code = TB_SUCCESS;
+  uint32_t k;
+  const g1a* row = nullptr;
+  if (!set_key(key_idx, tab_n, b, k))
+    code = TB_BAD_ENCODING;
+  else if (pk_code[k] != TB_SUCCESS || r == 0)
+    code = TB_PK_IS_INFINITY;
+  else if (key_idx) {
+    if (tab_comb) row = tab_comb + (size_t)k * TB_PKCOMB_ENTRIES;
+  } else if (pk_ref) {
+    const uint32_t ref = pk_ref[k];
+    if (ref & TB_PKREF_READY) row = ((ref & TB_PKREF_TABLE) ? tab_comb : cache_comb) + (size_t)(ref & TB_PKREF_ROW) * TB_PKCOMB_ENTRIES;
+  }
+  const unsigned long long served = __ballot(row != nullptr);  // the lanes here: the single-key sets of the wave
+  if (row && (threadIdx.x & 63u) == (uint32_t)__ffsll((long long)served) - 1u) atomicAdd(comb_stat, (unsigned long long)__popcll(served));
+  if (code == TB_SUCCESS) {
+    const g1j rp = row ? comb_mul_u64(row, r) : mul_u64_aff_w2_lds(pk_aff[k], r, &tab[threadIdx.x]);
+    if (!jac_to_aff(out, rp)) code = TB_PK_IS_INFINITY;
+  }
   P[i] = out;
   if (code != TB_SUCCESS) {
     set_code[i] = (uint8_t)code;

@@ -145,6 +145,14 @@ extern "C" __global__ void k_pkx_build(const uint32_t* __restrict__ keys, uint32
 extern "C" __global__ void k_pk_lookup(const uint8_t* __restrict__ pks, uint32_t K, uint32_t align, const uint32_t* __restrict__ slots, uint32_t mask, uint64_t seed, const uint32_t* __restrict__ tab_keys, const g1a* __restrict__ tab_aff, const uint8_t* __restrict__ tab_code, pkx_cache cache, g1a* __restrict__ pk_aff, uint8_t* __restrict__ pk_code, uint32_t* __restrict__ miss, unsigned long long* __restrict__ stat);
 extern "C" __global__ void k_pk_decompress_list(const uint8_t* __restrict__ pks, const uint32_t* __restrict__ list, g1a* __restrict__ pk_aff, uint8_t* __restrict__ pk_code, uint32_t* __restrict__ seen);
 extern "C" __global__ void k_pk_learn(const uint8_t* __restrict__ pks, uint32_t align, const uint32_t* __restrict__ list, const g1a* __restrict__ pk_aff, const uint8_t* __restrict__ pk_code, pkx_cache cache);
+// the per-key comb rows (tb_pkcomb.h): the lookup that also writes the keys' reference words, the learn kernel that
+// also builds the learned rows' combs, the table's build (k_pkindex.hip; the builders run TB_PKCOMB_BLOCK threads), and
+// k_set_pk_w2 reading the rows (k_w2_pk.hip)
+#define TB_PKCOMB_BLOCK 64
+extern "C" __global__ void k_pk_lookup_ref(const uint8_t* __restrict__ pks, uint32_t K, uint32_t align, const uint32_t* __restrict__ slots, uint32_t mask, uint64_t seed, const uint32_t* __restrict__ tab_keys, const g1a* __restrict__ tab_aff, const uint8_t* __restrict__ tab_code, pkx_cache cache, g1a* __restrict__ pk_aff, uint8_t* __restrict__ pk_code, uint32_t* __restrict__ miss, unsigned long long* __restrict__ stat, uint32_t* __restrict__ pk_ref, const uint8_t* __restrict__ cache_ready, uint32_t comb_cap, uint32_t tab_comb_on);
+extern "C" __global__ void k_pk_learn_comb(const uint8_t* __restrict__ pks, uint32_t align, const uint32_t* __restrict__ list, const g1a* __restrict__ pk_aff, const uint8_t* __restrict__ pk_code, pkx_cache cache, g1a* __restrict__ cache_comb, uint8_t* __restrict__ cache_ready, uint32_t comb_cap, unsigned long long* __restrict__ comb_stat);
+extern "C" __global__ void k_pk_comb_build(const g1a* __restrict__ tab_aff, const uint8_t* __restrict__ tab_code, uint32_t K, g1a* __restrict__ tab_comb, unsigned long long* __restrict__ comb_stat);
+extern "C" __global__ void k_set_pk_comb_w2(const uint32_t* __restrict__ pk_off, const g1a* __restrict__ pk_aff, const uint8_t* __restrict__ pk_code, const uint64_t* __restrict__ rand, uint32_t n, g1a* __restrict__ P, uint8_t* __restrict__ set_code, uint32_t* __restrict__ n_bad, const uint32_t* __restrict__ key_idx, uint32_t tab_n, uint32_t multi_wave, g1a* __restrict__ P2, const g1a* __restrict__ comb, const uint32_t* __restrict__ pk_ref, const g1a* __restrict__ cache_comb, const g1a* __restrict__ tab_comb, unsigned long long* __restrict__ comb_stat);
 extern "C" __global__ void k_pk_resolve(const uint8_t* __restrict__ pks, uint32_t n, uint32_t align, const uint32_t* __restrict__ slots, uint32_t mask, uint64_t seed, const uint32_t* __restrict__ tab_keys, uint32_t* __restrict__ idx_out);
 // the hash-point memo (k_msgmemo.hip; workgroups of TB_MEMO_BLOCK threads, TB_MEMO_CHUNKS threads per point): the words of
 // src and learn as tb_msgmemo.h spells them (pinned by static_assert in tb_lib.hip)

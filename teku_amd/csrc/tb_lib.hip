@@ -24,6 +24,7 @@
 #include "tb_hrow.h"
 #include "tb_host.h"
 #include "tb_pkindex.h"  // the key table's index over its key bytes: hash, probe step, probe bound
+#include "tb_pkcomb.h"   // the per-key comb rows: row size, reference words
 #include "tb_plan.h"  // every host-side decision: kernel choice, pair split, product levels, workspace layout, placement
 #include "tb_settle.h"  // the group-test descent of settling a failed batch
 #include "tb_pack.h"  // the staging image of a host batch: set kinds, layout, fill
@@ -134,6 +135,20 @@ struct dev_ctx {
   hbuf pk_seen;
   uint32_t* pk_seen_dev = nullptr;
   uint32_t pk_seen_K = 0;
+  // The per-key comb rows (tb_pkcomb.h), unless TBLS_PK_COMB=0
+  // (pkcomb_on, read by tbls_init).  pkcomb: the learned cache's region --
+  // pkcomb_cap ready bytes (one per cache row below the cap: TBLS_PK_COMB_KEYS,
+  // at most pkc_rows), then at a multiple of 256 bytes pkcomb_cap rows of
+  // TB_PKCOMB_ROW_BYTES -- allocated with the cache (pk_lookup_reserve), its
+  // ready bytes zeroed wherever the cache's slots are.  tab_comb: the loaded
+  // table's region, a row per table key (tbls_pk_table_load).  A region that
+  // cannot be allocated is given up (pkcomb_cap = 0 for the process; the table's
+  // until the next load) and the device verifies as without it.  pk_ref: the
+  // batch keys' reference words (k_pk_lookup_ref), a word per key, used and
+  // grown like pkx_miss.  pkcomb_stat: four 64-bit counters (tbls_pk_comb_stats).
+  bool pkcomb_on = false;
+  uint32_t pkcomb_cap = 0;
+  dbuf pkcomb, tab_comb, pk_ref, pkcomb_stat;
   // resident committees (tbls_committee_load): per slot TB_CM_STRIDE bytes of
   // cmt (members, bad-member mask, valid-member row, the valid members' sum,
   // the load pass's code and failure count); size 0: empty slot
@@ -319,12 +334,23 @@ inline key_src table_keys(const dev_ctx& c, const uint32_t* idx) { return {c.tab
 // those sets go to the wave-level aggregation
 // through a device-built work list (mlist / mcnt: n + 1 words of workspace).
 // P2 (nullable): signature-pair points -[r_i] g1 (comb: the device's table).
+// rows (nullable; pk_comb_rows): the device keeps comb rows for this batch's
+// key source, and the two-wave kernel's place is k_set_pk_comb_w2's.
+struct comb_rows {
+  const uint32_t* pk_ref;             // byte keys: the lookup's reference words (nullptr by index)
+  const g1a *cache_comb, *tab_comb;   // the regions' rows (nullptr: none)
+  unsigned long long* stat;
+};
 void launch_set_pk(hipStream_t s, uint32_t n, bool w2, uint32_t multi, const uint32_t* pk_off, const key_src& ks, const uint64_t* rand, g1a* P,
-                   uint8_t* set_code, uint32_t* n_bad, uint32_t* mlist, uint32_t* mcnt, g1a* P2, const g1a* comb) {
+                   uint8_t* set_code, uint32_t* n_bad, uint32_t* mlist, uint32_t* mcnt, g1a* P2, const g1a* comb, const comb_rows* rows = nullptr) {
   if (!n) return;
   const dim3 blk(TB_BLOCK), g((n + TB_BLOCK - 1) / TB_BLOCK);
-  hipLaunchKernelGGL(w2 ? k_set_pk_w2 : k_set_pk, g, blk, 0, s, pk_off, ks.aff, ks.code, rand, n, P, set_code, n_bad, ks.idx, ks.tab_n, multi, P2,
-                     comb);
+  if (w2 && rows)
+    hipLaunchKernelGGL(k_set_pk_comb_w2, g, blk, 0, s, pk_off, ks.aff, ks.code, rand, n, P, set_code, n_bad, ks.idx, ks.tab_n, multi, P2, comb,
+                       rows->pk_ref, rows->cache_comb, rows->tab_comb, rows->stat);
+  else
+    hipLaunchKernelGGL(w2 ? k_set_pk_w2 : k_set_pk, g, blk, 0, s, pk_off, ks.aff, ks.code, rand, n, P, set_code, n_bad, ks.idx, ks.tab_n, multi, P2,
+                       comb);
   if (!multi) return;
   (void)hipMemsetAsync(mcnt, 0, 4, s);
   hipLaunchKernelGGL(k_multi_list, g, blk, 0, s, pk_off, n, mlist, mcnt);
@@ -389,6 +415,23 @@ inline tb::pkx_cache pk_cache_view(const dev_ctx& c) {
           c.pkc.as<uint32_t>(0), c.pkc.as<unsigned long long>(8), c.pkc_seed};
 }
 
+// The comb regions (dev_ctx::pkcomb, tab_comb) as the kernels take them.
+inline size_t pkcomb_rows_off(const dev_ctx& c) { return align_up((size_t)c.pkcomb_cap); }  // behind the ready bytes
+inline bool pk_cache_comb_on(const dev_ctx& c) { return c.pkcomb_on && c.pkc_rows && c.pkc.p && c.pkcomb_cap && c.pkcomb.p; }
+inline bool pk_table_comb_on(const dev_ctx& c) { return c.pkcomb_on && c.tab_n && c.tab_comb.p; }
+// Byte keys on c get reference words from their lookup (k_pk_lookup_ref).
+inline bool pk_refs_on(const dev_ctx& c) { return pk_cache_comb_on(c) || (pk_table_index_on(c) && pk_table_comb_on(c)); }
+// The rows launch_set_pk reads for a batch whose keys are table indices
+// (by_index) or bytes that were looked up; false: the device has none for it.
+inline bool pk_comb_rows(const dev_ctx& c, bool by_index, comb_rows& r) {
+  if (by_index ? !pk_table_comb_on(c) : !(pk_lookup_on(c) && pk_refs_on(c))) return false;
+  r.pk_ref = by_index ? nullptr : c.pk_ref.as<const uint32_t>();
+  r.cache_comb = pk_cache_comb_on(c) ? c.pkcomb.as<const g1a>(pkcomb_rows_off(c)) : nullptr;
+  r.tab_comb = pk_table_comb_on(c) ? c.tab_comb.as<const g1a>() : nullptr;
+  r.stat = c.pkcomb_stat.as<unsigned long long>();
+  return true;
+}
+
 // Room for the miss list of a K-key stage, and the learned cache on its first
 // use; the caller holds the workspace (ws_acquire) and `s` orders every
 // earlier user of it, so growing drains s first, as the workspace does.  A
@@ -408,10 +451,25 @@ int pk_lookup_reserve(dev_ctx& c, uint32_t K, hipStream_t s) {
       HIPCHK(hipMemsetAsync(c.pkc.p, 0, pkc_zeroed_bytes(c), s));
     }
   }
+  // the cache's comb region with it: no row ready.  One that cannot be
+  // allocated is given up for the process too (TBLS_INIT_SHARE_DEVICES puts up
+  // to 32 contexts on one GPU): the device verifies as without comb rows.
+  if (c.pkcomb_on && c.pkcomb_cap && !c.pkcomb.p) {
+    c.pkcomb_cap = std::min(c.pkcomb_cap, c.pkc_rows);
+    if (!c.pkc.p || !c.pkcomb_cap || c.pkcomb.ensure(pkcomb_rows_off(c) + (size_t)c.pkcomb_cap * TB_PKCOMB_ROW_BYTES, true)) {
+      (void)hipGetLastError();
+      c.pkcomb.release();
+      c.pkcomb_cap = 0;
+    } else {
+      HIPCHK(hipMemsetAsync(c.pkcomb.p, 0, c.pkcomb_cap, s));
+    }
+  }
+  if (!pk_lookup_on(c)) return TBLS_SUCCESS;
   const size_t need = ((size_t)K + 1) * 4;
-  if (!pk_lookup_on(c) || need <= c.pkx_miss.cap) return TBLS_SUCCESS;
+  if (need <= c.pkx_miss.cap && (!pk_refs_on(c) || need <= c.pk_ref.cap)) return TBLS_SUCCESS;
   HIPCHK(hipStreamSynchronize(s));
-  return c.pkx_miss.ensure(need) ? TBLS_DEVICE_ERROR : TBLS_SUCCESS;
+  if (c.pkx_miss.ensure(need)) return TBLS_DEVICE_ERROR;
+  return pk_refs_on(c) && c.pk_ref.ensure(need) ? TBLS_DEVICE_ERROR : TBLS_SUCCESS;
 }
 
 // The key stage of K byte keys: affine points and validity codes into pk_aff /
@@ -430,14 +488,33 @@ int launch_pk_lookup(dev_ctx& c, hipStream_t s, const uint8_t* pks, uint32_t K, 
   uint32_t* miss = c.pkx_miss.as<uint32_t>();
   HIPCHK(hipMemsetAsync(miss, 0, 4, s));
   const bool tab = pk_table_index_on(c);
+  if (pk_refs_on(c)) {  // a device with comb rows: the keys' reference words too (k_set_pk_comb_w2 reads them)
+    const bool cc = pk_cache_comb_on(c);
+    hipLaunchKernelGGL(k_pk_lookup_ref, dim3((K + TB_PKX_BLOCK - 1) / TB_PKX_BLOCK), dim3(TB_PKX_BLOCK), 0, s, pks, K, pkx_align(pks),
+                       tab ? c.pkx_slots.as<const uint32_t>() : nullptr, tab ? c.pkx_cap - 1u : 0u, c.pkx_seed, c.tab_keys.as<const uint32_t>(),
+                       c.tab_aff.as<const g1a>(), c.tab_code.as<const uint8_t>(), pk_cache_view(c), pk_aff, pk_code, miss,
+                       c.pkx_stat.as<unsigned long long>(), c.pk_ref.as<uint32_t>(), cc ? c.pkcomb.as<const uint8_t>() : nullptr,
+                       cc ? c.pkcomb_cap : 0u, pk_table_comb_on(c) ? 1u : 0u);
+    return TBLS_SUCCESS;
+  }
   hipLaunchKernelGGL(k_pk_lookup, dim3((K + TB_PKX_BLOCK - 1) / TB_PKX_BLOCK), dim3(TB_PKX_BLOCK), 0, s, pks, K, pkx_align(pks),
                      tab ? c.pkx_slots.as<const uint32_t>() : nullptr, tab ? c.pkx_cap - 1u : 0u, c.pkx_seed, c.tab_keys.as<const uint32_t>(),
                      c.tab_aff.as<const g1a>(), c.tab_code.as<const uint8_t>(), pk_cache_view(c), pk_aff, pk_code, miss,
                      c.pkx_stat.as<unsigned long long>());
   return TBLS_SUCCESS;
 }
+// The comb builders' grid: workgroups of TB_PKCOMB_BLOCK threads that walk
+// their list with the grid's stride, at most 1,024 of them (the list's length
+// is only known on the device, and a batch without misses should launch little).
+inline dim3 pkcomb_grid(uint32_t K) { return dim3(std::min<uint32_t>((K + TB_PKCOMB_BLOCK - 1) / TB_PKCOMB_BLOCK, 1024u)); }
 void launch_pk_learn(dev_ctx& c, hipStream_t s, const uint8_t* pks, uint32_t K, const g1a* pk_aff, const uint8_t* pk_code) {
   if (!K || !c.pkc_rows) return;
+  if (pk_cache_comb_on(c)) {  // the append, and the comb rows of the keys it publishes
+    hipLaunchKernelGGL(k_pk_learn_comb, pkcomb_grid(K), dim3(TB_PKCOMB_BLOCK), 0, s, pks, pkx_align(pks), c.pkx_miss.as<const uint32_t>(), pk_aff,
+                       pk_code, pk_cache_view(c), c.pkcomb.as<g1a>(pkcomb_rows_off(c)), c.pkcomb.as<uint8_t>(), c.pkcomb_cap,
+                       c.pkcomb_stat.as<unsigned long long>());
+    return;
+  }
   hipLaunchKernelGGL(k_pk_learn, dim3((K + TB_PKX_BLOCK - 1) / TB_PKX_BLOCK), dim3(TB_PKX_BLOCK), 0, s, pks, pkx_align(pks),
                      c.pkx_miss.as<const uint32_t>(), pk_aff, pk_code, pk_cache_view(c));
 }
@@ -573,7 +650,10 @@ struct partial_run {
       if (const int rc = launch_byte_keys(c, sa, b.pks, bp.n_keys, W.pk_aff, W.pk_code, pre_lookup, false)) return rc;  // learnt behind the join (launch_partial)
       TB_EV(1, sa);
       TB_EV(2, sa);
-      launch_set_pk(sa, n, bp.w2, bp.multi, b.pk_off, keys, b.rand, set_P(), W.set_code, W.n_bad, W.mlist, W.mcnt, sig_P(), comb);
+      comb_rows rows;
+      const bool has_rows = pk_comb_rows(c, keys.idx != nullptr, rows);  // byte keys: the lookup wrote their references
+      launch_set_pk(sa, n, bp.w2, bp.multi, b.pk_off, keys, b.rand, set_P(), W.set_code, W.n_bad, W.mlist, W.mcnt, sig_P(), comb,
+                    has_rows ? &rows : nullptr);
     }
     if (bp.pp.grouped) group_sums();
     TB_EV(3, sa);
@@ -777,7 +857,12 @@ int launch_partial(dev_ctx& c, const tbls_dev_batch& b, hipStream_t s, void* par
   // held back the join: a 16,384-set tbls_batch_verify_each took 10.4 ms with
   // every key cached and 11.0 ms with none, against 9.4-9.5 ms without a cache
   // (DESIGN.md 3l).  The caller's stream waits for e_learn before ws_release,
-  // as for every stream: the kernel reads the workspace.
+  // as for every stream: the kernel reads the workspace.  With comb rows
+  //  the kernel here is k_pk_learn_comb, which also builds the
+  // published rows' comb entries and sets their ready bytes ahead of e_learn:
+  // nothing in this batch reads a comb row it builds (k_set_pk_comb_w2 goes by
+  // the references this batch's lookup wrote before), and the lookups of
+  // later launches start behind ws_acquire, so behind e_learn and the entries.
   const bool learns = bp.key == key_kind::decompress && bp.n_keys && c.pkc_rows;
   if (learns) {
     launch_pk_learn(c, run.sa, b.pks, bp.n_keys, W.pk_aff, W.pk_code);
@@ -1580,6 +1665,9 @@ extern "C" int tbls_init(int n_devices, uint32_t flags) {
   uint32_t cache_rows = 2097152u;
   if (const char* v = getenv("TBLS_PK_CACHE_KEYS")) cache_rows = (uint32_t)std::min<unsigned long long>(strtoull(v, nullptr, 10), 1ull << 28);
   if (!g_pk_lookup || (getenv("TBLS_PK_CACHE") && getenv("TBLS_PK_CACHE")[0] == '0')) cache_rows = 0;
+  const bool comb_on = !(getenv("TBLS_PK_COMB") && getenv("TBLS_PK_COMB")[0] == '0');
+  uint32_t comb_rows_cap = cache_rows;
+  if (const char* v = getenv("TBLS_PK_COMB_KEYS")) comb_rows_cap = (uint32_t)std::min<unsigned long long>(strtoull(v, nullptr, 10), cache_rows);
   if ((flags & TBLS_INIT_SHARE_DEVICES) && n_devices > 0 && n_devices <= 32)
     count = n_devices;  // contexts over the hardware devices round-robin
   else if (n_devices > 0 && n_devices < count)
@@ -1592,6 +1680,13 @@ extern "C" int tbls_init(int n_devices, uint32_t flags) {
       break;
     }
     c->pkc_rows = cache_rows;
+    // comb rows for the keys the device keeps, unless TBLS_PK_COMB=0; the
+    // cache's region holds TBLS_PK_COMB_KEYS rows (default: every cache row,
+    // 1,440 B each -- 3.0 GB at 2,097,152), allocated with the cache
+    if (comb_on && !c->pkcomb_stat.ensure(32) && hipMemset(c->pkcomb_stat.p, 0, 32) == hipSuccess) {
+      c->pkcomb_on = true;
+      c->pkcomb_cap = std::min(comb_rows_cap, cache_rows);
+    }
     // the hash-point memo's rows per device: TBLS_MSG_MEMO (default 0: off)
     if (const char* v = getenv("TBLS_MSG_MEMO")) c->memo.configure((uint32_t)std::min<unsigned long long>(strtoull(v, nullptr, 10), TB_MEMO_ROWS_MAX));
     g_ctx.push_back(c);
@@ -1763,6 +1858,18 @@ extern "C" int tbls_pk_table_load(const uint8_t* pks, size_t K, uint8_t* codes) 
                          c->tab_keys.as<const uint32_t>(), (uint32_t)K, c->pkx_slots.as<uint32_t>(), cap - 1u, seed);
       HIPCHK(hipGetLastError());
     }
+    // the table's comb region: a row per key, built from the points just
+    // decompressed; without the memory for it the table works as before
+    if (c->pkcomb_on) {
+      if (c->tab_comb.ensure(K * TB_PKCOMB_ROW_BYTES, true)) {
+        (void)hipGetLastError();
+        c->tab_comb.release();
+      } else {
+        hipLaunchKernelGGL(k_pk_comb_build, pkcomb_grid((uint32_t)K), dim3(TB_PKCOMB_BLOCK), 0, c->stream, c->tab_aff.as<const g1a>(),
+                           c->tab_code.as<const uint8_t>(), (uint32_t)K, c->tab_comb.as<g1a>(), c->pkcomb_stat.as<unsigned long long>());
+        HIPCHK(hipGetLastError());
+      }
+    }
     HIPCHK(hipStreamSynchronize(c->stream));
     c->tab_n = (uint32_t)K;
     if (index) {
@@ -1781,7 +1888,7 @@ extern "C" int tbls_pk_table_clear(void) {
     c->tab_n = 0;
     c->pkx_cap = 0;
     for (uint32_t& sz : c->cm_size) sz = 0;
-    for (dbuf* b : {&c->tab_aff, &c->tab_code, &c->tab_keys, &c->pkx_slots, &c->cmt}) b->release();
+    for (dbuf* b : {&c->tab_aff, &c->tab_code, &c->tab_keys, &c->pkx_slots, &c->cmt, &c->tab_comb}) b->release();
     if (c->pkx_stat.p) HIPCHK(hipMemset(c->pkx_stat.p, 0, 16));
     return TBLS_SUCCESS;
   });
@@ -1848,8 +1955,29 @@ extern "C" int tbls_pk_cache_clear(void) {
   return each_device(true, true, [&](dev_ctx* c) -> int {  // the last key stage has finished
     if (!c->pkc_rows || !c->pkc.p) return TBLS_SUCCESS;
     HIPCHK(hipMemsetAsync(c->pkc.p, 0, pkc_zeroed_bytes(*c), c->stream));
+    if (pk_cache_comb_on(*c)) HIPCHK(hipMemsetAsync(c->pkcomb.p, 0, c->pkcomb_cap, c->stream));  // no row's comb is ready
     HIPCHK(hipStreamSynchronize(c->stream));
     c->pk_seen_K = 0;  // and nothing is expected of the next batch's keys (pk_keys_known)
+    return TBLS_SUCCESS;
+  });
+}
+
+// The comb rows' counters, summed over the devices: sets whose [r] pk came
+// from a comb row, rows built for the learned caches, rows built for the
+// loaded tables, and the caches' comb rows' capacity (0: no region).
+extern "C" int tbls_pk_comb_stats(uint64_t out[4], int reset) {
+  const caller_device keep;
+  if (!out) return TBLS_BAD_ARGUMENT;
+  out[0] = out[1] = out[2] = out[3] = 0;
+  if (ensure_init()) return TBLS_DEVICE_ERROR;
+  return each_device(true, false, [&](dev_ctx* c) -> int {  // key stages queued on a caller's stream count too
+    if (!c->pkcomb_on) return TBLS_SUCCESS;
+    uint64_t v[3] = {0, 0, 0};
+    HIPCHK(hipMemcpyAsync(v, c->pkcomb_stat.p, sizeof v, hipMemcpyDeviceToHost, c->stream));
+    if (reset) HIPCHK(hipMemsetAsync(c->pkcomb_stat.p, 0, sizeof v, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < 3; i++) out[i] += v[i];
+    if (pk_cache_comb_on(*c)) out[3] += c->pkcomb_cap;
     return TBLS_SUCCESS;
   });
 }
@@ -1997,13 +2125,18 @@ static int run_each_resolved(dev_ctx* c, const SET* sets, size_t lo, size_t hi, 
   HIPCHK(hipMemsetAsync(n_bad, 0, 4, s));
   HIPCHK(hipMemsetAsync(set_code, 0, n, s));  // k_set_pk writes failures only
   // byte keys: from the table's index where it holds them, the others (or all) decompressed
-  if (const int rc = launch_byte_keys(*c, s, di + p.off_pks, K, (g1a*)(w + E.pk_aff), w + E.pk_code)) return rc;
+  // a cache with comb rows learns behind k_set_pk (the rows' build is the longer kernel, and nothing here reads it)
+  const bool learn_late = bytes_mode && pk_cache_comb_on(*c);
+  if (const int rc = launch_byte_keys(*c, s, di + p.off_pks, K, (g1a*)(w + E.pk_aff), w + E.pk_code, false, !learn_late)) return rc;
   if constexpr (bits_mode) {
     if (n) launch_set_pk_bits(s, n, keys, committee_src(*c, sets[lo].slot), rand, P, set_code, n_bad, nullptr, nullptr, 1u);
   } else {
+    comb_rows rows;
+    const bool has_rows = pk_comb_rows(*c, !bytes_mode, rows);
     launch_set_pk(s, n, use_w2(n), multi_key(n, p.K), (const uint32_t*)(di + p.off_pkoff), keys, rand, P, set_code, n_bad, (uint32_t*)(w + E.mlist), (uint32_t*)(w + E.mcnt),
-                  nullptr, nullptr);
+                  nullptr, nullptr, has_rows ? &rows : nullptr);
   }
+  if (learn_late) launch_pk_learn(*c, s, di + p.off_pks, K, (const g1a*)(w + E.pk_aff), w + E.pk_code);
   hipLaunchKernelGGL(k_sig_check, g, blk, 0, s, di + p.off_sigs, n, sig_aff, sig_use, sig_code, n_bad, 0u);
   if (!use_memo) {
     hipLaunchKernelGGL(k_set_hash, g, blk, 0, s, di + p.off_msgs, (const uint32_t*)(di + p.off_msgoff), di + p.off_dst, 43u, n, Q, skip);

@@ -128,6 +128,7 @@ struct plan_env {
   // TBLS_HASH_PLAN = "row_max,quad_max,duo_max" (A/B; 0 disables a kernel)
   uint32_t row_max = TB_HASH_ROW_MAX, quad_max = TB_HASH_QUAD_MAX, duo_max = TB_HASH_DUO_MAX;
   bool w2 = true;  // TBLS_W2=0: the one-wave kernels at every size
+  uint32_t w2_min = TB_W2_MIN;  // TBLS_W2_MIN: the two-wave kernels from this many sets (tuning; tests reach them at a few hundred sets)
   // Small batches (<= TB_HASH_WAVE_MAX sets) run the key, signature and hash
   // stages, and multi-key aggregation, on the lane-cooperative kernels
   // (k_kcoop.hip, k_hwave.hip k_set_hash_coop); TBLS_COOP=0 selects the
@@ -169,6 +170,11 @@ struct plan_env {
     }
   }
   void parse_w2(const char* v) { w2 = !(v && v[0] == '0'); }
+  void parse_w2_min(const char* v) {
+    if (!v) return;
+    const long m = atol(v);
+    if (m >= 1) w2_min = (uint32_t)std::min<long>(m, 0x7fffffffL);
+  }
   void parse_coop(const char* v) { coop = !(v && v[0] == '0'); }
   void parse_shard_min(const char* v) {
     if (!v) return;
@@ -199,6 +205,7 @@ struct plan_env {
     e.parse_acc_plan(getenv("TBLS_ACC_PLAN"));
     e.parse_hash_plan(getenv("TBLS_HASH_PLAN"));
     e.parse_w2(getenv("TBLS_W2"));
+    e.parse_w2_min(getenv("TBLS_W2_MIN"));
     e.parse_coop(getenv("TBLS_COOP"));
     e.parse_shard_min(getenv("TBLS_SHARD_MIN"));
     e.parse_group_min(getenv("TBLS_GROUP_MIN"));
@@ -460,7 +467,7 @@ inline int line_group(uint32_t n_main, const plan_env& env = plan_env::get()) {
   if (env.duo_max && 2ull * n_main <= TB_GROUP_LANES) return 2;
   return 1;
 }
-inline bool use_w2(uint32_t n, const plan_env& env = plan_env::get()) { return env.w2 && n >= TB_W2_MIN; }
+inline bool use_w2(uint32_t n, const plan_env& env = plan_env::get()) { return env.w2 && n >= env.w2_min; }
 // Sets of several keys (n_keys > n: configs 2/3) go to a wave-level
 // aggregation after the one-thread kernel: 2 the lane-cooperative one (32
 // rows per set, k_kcoop.hip, with the set's -[r] g1), 1 the one-wave-per-set

@@ -161,6 +161,7 @@ _SIGS = {
     "tbls_pk_lookup_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
     "tbls_pk_cache_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
     "tbls_pk_cache_clear": (ctypes.c_int, []),
+    "tbls_pk_comb_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
     "tbls_msg_memo_configure": (ctypes.c_int, [ctypes.c_uint32]),
     "tbls_msg_memo_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
     "tbls_msg_memo_clear": (ctypes.c_int, []),

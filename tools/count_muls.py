@@ -19,6 +19,19 @@ OPS.update(STAGE_PK=24, STAGE_SET_PK=25, STAGE_SET_SIG=26, STAGE_SET_HASH=27, G2
 MADS_MUL, MADS_SQR, MADS_F2 = 392, 301, 980  # v_mad_u64_u32 per 14 x 29-bit Montgomery product / squaring (tb_fp.h), lazy Fp2 product (tb_tower.h)
 
 
+def comb_counts():
+    """(products of one [r] pk through a comb row, products of one row's build)."""
+    import subprocess
+
+    d = os.path.join(ROOT, "tests", "native", "_build")
+    os.makedirs(d, exist_ok=True)
+    exe = os.path.join(d, "pkcomb_count")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-DTB_COUNT_MULS", "-I", os.path.join(ROOT, "teku_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "native", "pkcomb_check.cpp"), "-o", exe])
+    rows = dict((ln.split()[0], float(ln.split()[1])) for ln in subprocess.check_output([exe, "count"], text=True).splitlines())
+    return rows["set_pk_comb"], rows["pk_comb_build"]
+
+
 def main():
     lib = ctypes.CDLL(os.path.join(ROOT, "tests", "native", "_build", "libtbhostsim_count.so"))
     fn = lib.tbls_hostsim_test_ops
@@ -129,6 +142,12 @@ def main():
     # per single-signer set (the unit of the headline metric), excluding the once-per-batch final exp
     res["per_set_total"] = sum(res[k] for k in ["pk_decompress", "set_pk", "set_sig", "set_hash", "g2_sum"]) + res["pairs_per_set"] * (
         res["miller"] + res["fp12_prod"])
+    # The same set through a per-key comb row (tb_pkcomb.h: comb_mul_u64 +
+    # jac_to_aff, k_set_pk_comb_w2's path for a key the device keeps), and the
+    # row's one-time build (comb_build): counted by tests/native/pkcomb_check.cpp
+    # on the same instrumentation.  Not part of per_set_total, which stays the
+    # work of a batch whose keys are new.
+    res["set_pk_comb"], res["pk_comb_build"] = comb_counts()
     res["note"] = ("per set of the large-batch path (n = 131072, the bench config): set_sig = decode + G2 check (k_sig_check), "
                    "g2_sum = bucket sums + bucket pairs' trees/affine; miller per pair (pairs_per_set pairs per set). "
                    "Small batches add set_pk_sigpair per set and one signature pair per set instead of the bucket pairs.")
