@@ -1,6 +1,7 @@
-"""The segmented Miller accumulator (k_lines.hip k_miller_accs + the segment
+"""The segmented Miller accumulator (k_lines.hip k_miller_accs_lds + the segment
 product trees + k_fp12_seg_combine_coop) computes the same Fp12 product as the
-unsegmented k_miller_acc1 / acc2: the partial record of a seeded batch, its
+unsegmented k_miller_acc1 / acc2 (each kernel against a plain reference at its
+own output: tests/test_gpu_pair_stage.py): the partial record of a seeded batch, its
 12 coordinates canonicalized mod p, is identical under every accumulator plan
 (TBLS_ACC_PLAN=0: the unsegmented kernels; forced pairs-per-thread x segment
 counts "per,nseg"; the default plan), on the per-set signature-pair path
